@@ -14,11 +14,19 @@ an "error" field, leaves each rank's stderr in gpurun_out/rank<r>.err and exits 
 One "step" = one pass of the whole hot path (VCRNet.forward: LPDNet kNN-graph embedding -> Transformer
 virtual-correspondence block -> soft correspondences -> SVD rigid solve) over one batch of 16 synthetic pairs of
 N=1024 points PER GPU (BASELINE.json configs[1]; weak scaling), inputs already resident in HBM, plus -- for N > 1 --
-the RCCL all-gather of the per-rank (R, t).  The K-step timed block (barrier + synchronize on both sides, MAX over
-ranks) is repeated until >= 12 s of GPU time have been spent so that external samplers see the load; the MEDIAN block
-is reported and every block's time is listed.  The per-launch HIP events behind `roofline` / `stages` are recorded
-inside those same timed blocks, on every 5th step (--trace-every): ~35 event records cost ~2 % of a step that carries
-them.  Prints ONE JSON line on rank 0.
+the RCCL all-gather of the per-rank (R, t).  A plain run sets up, runs --warmup steps, times ONE block of exactly
+--steps steps (barrier + synchronize on both sides, MAX over ranks) and prints ONE JSON line on rank 0: `value`
+(pairs/s) and `ms_per_step` come from that block.
+
+--full adds everything beyond that headline, as the run did before the split: the K-step block is repeated until
+>= 12 s of GPU time have been spent (--min-seconds) so that external samplers see the load, the MEDIAN block is
+reported and every block's time is listed; the per-launch HIP events behind `roofline` / `stages` are recorded inside
+those same timed blocks, on every 5th step (--trace-every: ~35 event records cost ~2 % of a step that carries them);
+one GPU also gets `other_configs`, and every run the `parity_ledger` and (one GPU) the `cpu_baseline`.
+
+--dump-outputs DIR: after the timed steps, what the last of them returned (vcrnetIter's six tensors, and with N > 1
+the gathered poses) is written as DIR/<name>.npy in float32 / float64 by rank 0; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -61,19 +69,25 @@ def parse(argv=None):
                     help="point in weight space (vcrnet_amd.weights.regime_weights; lpdnet only): default = seed 1234 + the "
                          "LPD-pretrained emb_nn (the headline), randemb = a random feature extractor -- what the ordered kNN "
                          "search's per-cloud guard must cope with")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not the headline: repeated timed blocks (--min-seconds), the per-launch "
+                         "events behind roofline / stages, other_configs, the parity ledger and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget-s", type=float, default=100.0,
                     help="wall-clock budget of the CPU-baseline thread sweep (each thread count: one warm-up, then up "
                          "to 5 timed runs while the budget lasts)")
     ap.add_argument("--cpu-baseline-full", action="store_true",
                     help="SURVEY 8d protocol without a budget: every thread count, B = --batch, median of 5")
-    ap.add_argument("--min-seconds", type=float, default=12.0, help="repeat the timed K-step block for this long")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="repeat the timed K-step block for this long (default: 12 with --full, else one block)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="the default single-GPU run appends `other_configs` (BASELINE configs[2] -- also with every pass recomputing "
+                    help="--full on one GPU appends `other_configs` (BASELINE configs[2] -- also with every pass recomputing "
                          "both clouds --, configs[3]'s per-GPU share, configs[4] and the bf16x3+sdpa line, --other-seconds of timed blocks each) AFTER the headline has "
                          "been measured; this switch leaves them out")
     ap.add_argument("--other-seconds", type=float, default=2.0, help="timed seconds per entry of `other_configs`")
-    ap.add_argument("--stages", action="store_true", help="print the per-launch table to stderr")
+    ap.add_argument("--stages", action="store_true", help="print the per-launch table to stderr (needs --full)")
     ap.add_argument("--trace-every", type=int, default=5,
                     help="record the per-launch HIP events (roofline / stage table) on every N-th step of each timed "
                          "block: the ~35 event records cost ~2 %% of a step they are recorded in; 1 = every step")
@@ -96,7 +110,12 @@ def parse(argv=None):
     ap.add_argument("--linear-bm", type=int, default=0, choices=[0, 96, 128], help="tile height of the fp32 linears (0 = the library's choice)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl == RCCL on ROCm); gloo only "
                                                       "for exercising the multi-rank control flow on a 1-GPU box")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.stages and not a.full:
+        ap.error("--stages prints the per-launch events that only --full records")
+    if a.min_seconds is None:
+        a.min_seconds = 12.0 if a.full else 0.0
+    return a
 
 
 def model_args(partial=False, emb_nn="lpdnet"):
@@ -420,6 +439,7 @@ def measure(a, ctx, min_seconds):
     assert src.shape == (B, 3, N) and src.is_cuda, src.shape
 
     gather_ev = []            # (start, end) HIP events around the collective, on the stream the forward was enqueued on
+    last = {}                 # --dump-outputs: what the latest step returned (references only, nothing is copied)
 
     def step(trace=None):
         net.launch_trace = trace                # profiling hook of the module: per-launch HIP events on traced steps
@@ -434,6 +454,8 @@ def measure(a, ctx, min_seconds):
             if trace is not None:
                 e1.record()
                 gather_ev.append((e0, e1))
+        if a.dump_outputs:
+            last.update(out=out, pose=pose)
         return pose
 
     # one-time initialisation, not a warm-up step: the first call loads the code objects, packs / folds the weights,
@@ -443,8 +465,8 @@ def measure(a, ctx, min_seconds):
     for _ in range(a.warmup):
         step()
     # steps of a block that carry per-launch events -- never the first ones behind the fence (the queue is empty there and
-    # the device may have idled: a traced step must look like every other step of the block)
-    traced_steps = list(range(min(2, a.steps - 1), a.steps, max(1, a.trace_every)))
+    # the device may have idled: a traced step must look like every other step of the block); --full only
+    traced_steps = list(range(min(2, a.steps - 1), a.steps, max(1, a.trace_every))) if a.full else []
     traces = {i: native.LaunchTrace() for i in traced_steps}
     nt = len(traced_steps)
 
@@ -481,6 +503,8 @@ def measure(a, ctx, min_seconds):
     while sum(blocks) < min_seconds and len(blocks) < 1000:
         blocks.append(timed_block())
     elapsed = float(np.median(blocks))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last["out"], last["pose"] if world > 1 else None)
     multi = None
     if world > 1:
         # what the first real 8-GPU run needs to explain itself: every rank's own median step time (before the MAX), the
@@ -506,6 +530,9 @@ def measure(a, ctx, min_seconds):
                                            + ("" if a.backend == "nccl" else
                                               f"; backend {a.backend}: the poses are staged through the host, so this is a "
                                               "device-to-host copy + a CPU collective, not RCCL"))}
+        if not nt:                              # no traced steps (a plain run): the collective was not timed
+            for k_ in ("all_gather_ms", "all_gather_ms_per_rank", "all_gather_ms_worst"):
+                multi[k_] = None
         # which transport carried the collective (rank 0's RCCL debug log, see setup_rank): xgmi_only is True only when
         # every channel is P2P and the topology RCCL detected lists XGMI links; False as soon as a NET/ or SHM/ transport
         # appears; None when there is no log to read (gloo, or RCCL wrote nothing)
@@ -534,7 +561,7 @@ def measure(a, ctx, min_seconds):
             r = rows.setdefault(name, [0.0, fl, by, 0, gb])
             r[0] += ms; r[3] += 1
         tr.close()
-    if rank == 0:
+    if rank == 0 and nt:                        # the per-launch figures: only a run with traced steps (--full) has them
         dom = max(fam_ms, key=fam_ms.get)
         bound = workmodel.FAMILY_BOUND[dom]
         if bound == "mfma":
@@ -625,6 +652,9 @@ def measure(a, ctx, min_seconds):
                 ms = r[0] / r[3]
                 print(f"{n:28s} {ms:8.3f} ms  {r[1] / ms / 1e9:8.2f} TF/s  {r[2] / ms / 1e6:9.1f} GB/s"
                       + (f"  (+{r[4] / ms / 1e6:8.1f} GB/s neighbour gathers, L2 / LDS)" if r[4] else ""), file=sys.stderr)
+    if rank == 0:
+        if not nt:                              # (with traces, `reuse` also checks that the launches ran on the source alone)
+            reuse = a.iters > 1 and a.emb_nn == "lpdnet" and bool(getattr(net, "iter_reuse", False))
         pairs = B * world * a.steps
         line = {
             "metric": "point-cloud pairs/sec (N=%d, batch %d per GPU)" % (Nfull, B) if not a.strong else
@@ -647,22 +677,49 @@ def measure(a, ctx, min_seconds):
             "timed_blocks": {"count": len(blocks), "steps_per_block": a.steps, "reported": "median",
                              "seconds": [round(b, 6) for b in blocks[:64]],
                              "per_launch_events": f"steps {traced_steps} of every block (a step that carries the ~35 event "
-                                                  "records runs ~2 % longer: the stage times sum to that step, not to ms_per_step)"},
-            "roofline": roof,
-            # the traced launches' HIP-event durations, summed, over the timed block's ms_per_step: what share of a step the
-            # launch table explains.  Below ~0.97 the steps are not back-to-back kernels (host-bound enqueue, idle gaps) or
-            # traced steps run at another clock than untraced ones -- the per-launch rates then overstate the steady state
-            "accounted_frac": (total_ms / nt) / (elapsed / a.steps * 1e3),
-            "stages": stages,
-            "flops_per_pair_reference": workmodel.reference_flops_per_pair(N, a.k)["total"],
+                                                  "records runs ~2 % longer: the stage times sum to that step, not to ms_per_step)"
+                                                  if nt else "none (--full records them)"},
         }
-        if emb_stage is not None:          # the stage BASELINE prices exists only for the kNN-graph LPDNet embedding
-            line["knn_edgeconv_stage"] = emb_stage
+        if nt:
+            line.update({
+                "roofline": roof,
+                # the traced launches' HIP-event durations, summed, over the timed block's ms_per_step: what share of a step the
+                # launch table explains.  Below ~0.97 the steps are not back-to-back kernels (host-bound enqueue, idle gaps) or
+                # traced steps run at another clock than untraced ones -- the per-launch rates then overstate the steady state
+                "accounted_frac": (total_ms / nt) / (elapsed / a.steps * 1e3),
+                "stages": stages,
+                "flops_per_pair_reference": workmodel.reference_flops_per_pair(N, a.k)["total"],
+            })
+            if emb_stage is not None:      # the stage BASELINE prices exists only for the kNN-graph LPDNet embedding
+                line["knn_edgeconv_stage"] = emb_stage
         if multi is not None:
             line["multi_gpu"] = multi
         line["_weights"], line["_Nfull"], line["_B"] = w, Nfull, B          # for the caller's CPU baseline; stripped
         return line
     return None
+
+
+DUMP_BYTES = 64 << 20
+DUMP_NAMES = ("src_k", "corr_k", "rotation_ab", "translation_ab", "rotation_ba", "translation_ba")   # vcrnetIter's returns
+
+
+def dump_outputs(path, out, pose_all=None):
+    """--dump-outputs: vcrnetIter's six returns of the last timed step (and, N > 1, the poses gathered over the ranks) as
+    <path>/<name>.npy, float32 / float64 as computed (integer tensors as float64).  Outputs beyond DUMP_BYTES in all are
+    thinned to a fixed, seeded sample of their flat elements (written with its indices, <name>.index.npy)."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {n: t for n, t in zip(DUMP_NAMES, out) if t is not None}
+    if pose_all is not None:
+        arrs["poses_all_ranks"] = pose_all
+    arrs = {n: t.detach().cpu().numpy() for n, t in arrs.items()}
+    arrs = {n: v if v.dtype in (np.float32, np.float64) else v.astype(np.float64) for n, v in arrs.items()}
+    share = DUMP_BYTES // (2 * len(arrs)) - 128    # a sampled array also writes its indices; 128 = an .npy header
+    for n, v in arrs.items():
+        if v.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, share // 8, replace=False))
+            np.save(os.path.join(path, n + ".index.npy"), idx.astype(np.float64))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(path, n + ".npy"), v)
 
 
 # the BASELINE configs that are not the headline, and the labelled split-arithmetic line, as bench.py flag overrides
@@ -689,14 +746,14 @@ def run_rank(a):
     line = measure(a, ctx, a.min_seconds)
     if ctx.rank == 0:
         w, Nfull, B = line.pop("_weights"), line.pop("_Nfull"), line.pop("_B")
-        if ctx.world == 1 and is_headline(a) and not a.no_other_configs:
+        if ctx.world == 1 and is_headline(a) and a.full and not a.no_other_configs:
             # measured AFTER the headline (which is untouched by them), same process, same protocol, shorter blocks
             others = []
             for tag, over in OTHER_CONFIGS:
                 b = argparse.Namespace(**vars(a))
                 for k_, v_ in over.items():
                     setattr(b, k_, v_)
-                b.stages = False
+                b.stages, b.dump_outputs = False, None
                 t0 = time.perf_counter()
                 o = measure(b, ctx, a.other_seconds)
                 for k_ in ("_weights", "_Nfull", "_B"):
@@ -713,8 +770,9 @@ def run_rank(a):
                                "wall_s": round(time.perf_counter() - t0, 2)})
                 torch.cuda.empty_cache()
             line["other_configs"] = others
-        line["parity_ledger"] = parity_ledger(a.linear_mode)
-        if ctx.world == 1 and not a.no_cpu_baseline:
+        if a.full:
+            line["parity_ledger"] = parity_ledger(a.linear_mode)
+        if ctx.world == 1 and a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(w, B, Nfull, a.k, a.partial, a.iters, a.cpu_budget_s, a.cpu_baseline_full)
         os.write(ctx.json_fd, (json.dumps(line) + "\n").encode())
     if ctx.world > 1:

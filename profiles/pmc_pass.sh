@@ -12,7 +12,7 @@ IFS=',' read -ra GROUPS_ <<< "$*"
 i=0
 for g in "${GROUPS_[@]}"; do
   d=$OUT/pmc_${TAG}_$i
-  rocprofv3 --kernel-trace --output-format csv --pmc $g -d $d -- python3 bench.py --no-cpu-baseline --no-other-configs --steps 3 --warmup 1 --min-seconds 0.1 $BENCH_ARGS > /dev/null 2> $OUT/${TAG}_pmc_$i.err
+  rocprofv3 --kernel-trace --output-format csv --pmc $g -d $d -- python3 bench.py --full --no-cpu-baseline --no-other-configs --steps 3 --warmup 1 --min-seconds 0.1 $BENCH_ARGS > /dev/null 2> $OUT/${TAG}_pmc_$i.err
   python3 - "$d" > $OUT/${TAG}_pmc_$i.txt <<'PY'
 import csv, glob, sys, collections
 rows = collections.defaultdict(lambda: collections.defaultdict(list))
