@@ -199,6 +199,7 @@ __global__ __launch_bounds__(256) void zero_i32_kernel(int32_t* p, long n) {
   if (i < n) p[i] = 0;
 }
 extern "C" int vcr_linear_shapes_(const vcr_linear_args* a, const vcr_linear_args* b, int* shape_a, int* shape_b);   // linear.hip
+extern "C" int vcr_knn_forms_(const vcr_knn_args* a, const vcr_knn_args* b, int* ordered, int* inline_a, int* inline_b);  // knn.hip
 
 struct Runner {
   hipStream_t stream; vcr_trace* tr; int rc = 0;
@@ -325,7 +326,9 @@ struct Runner {
     if (rc) return;
     mark(nm);
     a.tie_zeroed = 1;
-    if (defer && n_deferred < 2 && !vcr_knn_ties_inline(&a)) {          // (inline: the launch replays its own ties)
+    int inl = 0;                                         // (inline: the launch replays its own ties; bad args: the launch says so)
+    (void)vcr_knn_forms_(&a, nullptr, nullptr, &inl, nullptr);
+    if (defer && n_deferred < 2 && !inl) {
       a.tie_defer = 1;
       deferred[n_deferred++] = a;
     }
@@ -338,8 +341,10 @@ struct Runner {
     a64.tie_zeroed = a3.tie_zeroed = 1;
     a64.tie_defer = a3.tie_defer = 1;
     n_deferred = 0;                                      // (a launch that replays its ties itself owes nothing)
-    if (!vcr_knn_ties_inline(&a64)) deferred[n_deferred++] = a64;
-    if (!vcr_knn_ties_inline(&a3)) deferred[n_deferred++] = a3;
+    int inl64 = 0, inl3 = 0;
+    (void)vcr_knn_forms_(&a64, &a3, nullptr, &inl64, &inl3);
+    if (!inl64) deferred[n_deferred++] = a64;
+    if (!inl3) deferred[n_deferred++] = a3;
     ok(vcr_knn_pair_f32(&a64, &a3, stream));
   }
   // one replay launch for every kNN deferred so far: to be called before the first consumer of any of their indices
@@ -627,8 +632,9 @@ int forward_impl(const vcr_vcrnet_weights* W, const vcr_vcrnet_io* io, void* wor
     // wave skip the tiles whose balls cannot hold a neighbour -- measured (profiles/rounds4-5/r5o_knn_ordered.txt) 416 -> 295 + 45 us
     // (ranking) at 32 x 2048, 2970 -> 1850 + 93 at 64 x 4096, k = 40; at 1024 points the plain scan is faster (120 vs 143 + 30).
     // Its arrays live in the unused part of w.emb (free until conv3; feat64t is its first M2 x 64 floats).
+    int pair_ordered = 0;                                // (the library's choice: only the pair's fused 16-query form reads the ranking)
     if (R.rc == 0 && W->E >= 256 && N >= KNN_ORDERED_MIN_N && N <= 8192 && (k == 20 || k == 40) && W->knn_waves == 0 &&
-        (long)Bq * ((N + 15) / 16) >= 1024) {            // (fewer query groups: vcr_knn_pair_f32 takes its small-grid kernels)
+        vcr_knn_forms_(&a64, &a3, &pair_ordered, nullptr, nullptr) == VCR_OK && pair_ordered) {
       const size_t m = (size_t)M2, mt = (size_t)2 * B * ((N + 15) / 16);
       float* base = w.emb + m * 64;
       float* feat_p = base;                 base += m * 64;

@@ -62,7 +62,6 @@ struct GeomCol16;
 // launch 151.4 -> 147.7 us at BASELINE configs[1], 147.5 -> 136.7 at N = 768 (configs[2]), 439 -> 432 at N = 2048.
 constexpr int KNN_ORD_NEAR = 4;                          // tiles on either side of the own one scanned first
 constexpr int KNN_ORD_MAX_TILES = 512;                   // the ordered search's wave-uniform tile mask: clouds of up to 8192 points
-constexpr int KNN_ORD_MODE = 0;                          // timing ablations of the ordered search: 1 = its loop over ALL tiles, 2 = the plain loop over the ranked rows
 constexpr int KNN_PEND_K40 = 96;                         // k = 21 .. 40 (lists of 42)
 constexpr int KNN_PEND_COL16 = 72;                       // (the sweeps: profiles/experiments/probe_build.py --set NAME=VALUE)
 template <class G, int KS> constexpr int pend_of() {
@@ -797,8 +796,7 @@ __device__ __forceinline__ void knn64c_body(const vcr_knn_args& a, int bx, int b
   // the scores priced in (m: 3e-5 of the norms involved, ~4x the worst case of a 64-term fp32 dot product), so a tile is dropped
   // only when every one of its rows would fail the filter `score > thr` for every query of the wave.  (3) the remaining tiles
   // are scanned like any others.  Visiting order and omissions of entries below the final threshold do not change the kept set.
-  [[maybe_unused]] auto ordered_scan_impl = [&](auto full_tag) {
-    constexpr bool FULL = decltype(full_tag)::value;
+  [[maybe_unused]] auto ordered_scan_impl = [&](auto) {
     constexpr int NEAR = KNN_ORD_NEAR;
     const int T = ntiles, g = q0 / CT;
     int lo = max(0, g - NEAR), hi = min(T, g + NEAR + 1);
@@ -851,11 +849,7 @@ __device__ __forceinline__ void knn64c_body(const vcr_knn_args& a, int bx, int b
         tA = nA; tB = nB;
       }
     };
-    if constexpr (FULL) { lo = 0; hi = T; }
-    if constexpr (FULL) {
-      int t = lo;
-      scan_seq([&]() { return t < hi ? t++ : -1; });
-    } else {
+    {
       // own tile first, then outwards (g + 1, g - 1, g + 2, ...): along the curve the tiles get closer as the scan approaches
       // the wave's rank -- in rank order every candidate would beat the threshold the previous ones left (a streaming top-k's
       // worst case: the plain loop over ranked rows takes 1.9x its time over unranked ones)
@@ -870,7 +864,7 @@ __device__ __forceinline__ void knn64c_body(const vcr_knn_args& a, int bx, int b
         return -1;
       });
     }
-    if (FULL || hi - lo >= T) return;
+    if (hi - lo >= T) return;
     sel.drain();                                         // thr = the (k + 2)-th best of the near candidates, exactly
     constexpr int NEEDW = KNN_ORD_MAX_TILES / 64;                          // tiles still to visit: one bit each (T <= 512)
     unsigned long long need[NEEDW];
@@ -959,8 +953,9 @@ __device__ __forceinline__ void knn64c_body(const vcr_knn_args& a, int bx, int b
       });
     }
   };
+  // (a generic lambda behind a wrapper, as the code was measured: a plain one is the same search but changes the ORD kernels' register
+  // allocation)
   [[maybe_unused]] auto ordered_scan = [&]() { ordered_scan_impl(std::false_type{}); };
-  [[maybe_unused]] auto ordered_scan_full = [&]() { ordered_scan_impl(std::true_type{}); };
   // C == 4: filter floor from a sample (see SampleNet): the first 256 candidates' values only -- 16 MFMAs -- give a
   // threshold the scan proper starts with (the VALU kernel: 75 -> 65 us; distances are one MFMA per tile here, so the
   // pre-pass costs next to nothing.  C == 64 recomputes 17 MFMAs per sampled tile: measured a wash, off).
@@ -980,9 +975,7 @@ __device__ __forceinline__ void knn64c_body(const vcr_knn_args& a, int bx, int b
   }
   if constexpr (ORD) {
     if (!ord) scan_all();
-    else if constexpr (KNN_ORD_MODE == 0) ordered_scan();
-    else if constexpr (KNN_ORD_MODE == 1) ordered_scan_full();
-    else scan_all();
+    else ordered_scan();
   } else {
     scan_all();
   }
@@ -1628,29 +1621,9 @@ extern "C" size_t vcr_knn_tie_work_bytes(int N) {
 extern "C" size_t vcr_knn_tie_slot_bytes(int B, int N) {
   return (B > 0 && N > 0) ? (size_t)B * ((N + 63) / 64) * 16 * (size_t)N : 0;
 }
-static int ties_inline(const vcr_knn_args* a);
-// a replay is owed (tie_scratch) but the rows need global scratch that the caller did not provide
-static bool tie_work_missing(const vcr_knn_args* a) {
-  const size_t need = vcr_knn_tie_work_bytes(a->N);
-  if (ties_inline(a) == 2) return false;                 // (the launch replays its ties itself, in its workgroups' slots)
-  return a->tie_scratch && need && (!a->tie_work || a->tie_work_bytes < need || ((uintptr_t)a->tie_work & 15));
-}
-
 // the part of vcr_knn_args every caller must pass: through tie_cap (everything behind it is optional, zero = automatic)
 static int knn_take(const vcr_knn_args* user, vcr_knn_args* mine) {
   return vcr_take_args(user, mine, offsetof(vcr_knn_args, waves));
-}
-
-extern "C" int vcr_knn_ties_f32(const vcr_knn_args* ua, const vcr_knn_args* ub, vcr_stream_t stream) {
-  vcr_knn_args na, nb;
-  if (knn_take(ua, &na) || (ub && knn_take(ub, &nb))) return VCR_EINVAL;
-  const vcr_knn_args *a = &na, *b = ub ? &nb : nullptr;
-  if (!a->x || !a->idx || !a->tie_scratch || a->tie_cap < 1) return VCR_EINVAL;
-  if (b && (!b->x || !b->idx || !b->tie_scratch || b->tie_cap < 1)) return VCR_EINVAL;
-  if (tie_work_missing(a) || (b && tie_work_missing(b))) return VCR_EUNSUPPORTED;
-  const size_t la = tiebreak_launch_lds(a->N), lb = b ? tiebreak_launch_lds(b->N) : 0, lds = la > lb ? la : lb;
-  if (b) return launch<knn_tiebreak2_kernel>(dim3(TB_BLOCKS, 2), dim3(256), lds, (hipStream_t)stream, *a, *b);
-  return launch<knn_tiebreak_kernel>(dim3(TB_BLOCKS), dim3(256), lds, (hipStream_t)stream, *a);
 }
 
 // Which feature-space kernel: 16-query waves on 16x16x4 MFMAs (knn64c_body) or 32-query waves on 32x32x2 (knn64_body).
@@ -1665,46 +1638,16 @@ static bool use_col16(const vcr_knn_args* a) {
   if (a->waves != 0) return false;
   return (long)((a->N + 15) / 16) * a->B >= 1024;
 }
-
-// In-kernel tie replay: the launch's workgroups are 4 waves of 16 queries (knn64c_body / knn3_body with S = 1) and a row's
-// replay image fits beside nothing else in <= 40 KB of LDS (N <= ~2400): see replay_block_ties.
-static int knn_s(const vcr_knn_args* a);
-static size_t knn_log_bytes(const vcr_knn_args* a) {       // LDS of the four logs of such a workgroup
-  const bool k20 = a->k <= 20;
-  const size_t col16 = (size_t)4 * 2 * ((k20 ? pend_of<GeomCol16, 22>() : pend_of<GeomCol16, 42>()) + 4) * 16 * 4;
-  if (a->C == 64) return col16;
-  // the Cartesian search: unsplit = the MFMA body (same log as the feature-space kernel), split = the quad kernel
-  return knn_s(a) == 1 ? col16 : (size_t)4 * 2 * ((k20 ? pend_of<GeomQuad, 22>() : pend_of<GeomQuad, 42>()) + 1) * 16 * 4;
-}
-static int knn_s(const vcr_knn_args* a) {                  // candidate split of the 32-query / Cartesian kernels (vcr_knn_f32)
+// Candidate split S of the 32-query and Cartesian kernels: S waves of a workgroup share one group of queries and split its
+// candidates.  The selection work grows with the number of lists (S per query), and measured on MI355X a second wave per SIMD
+// bought with S = 2 only breaks even, so S stays 1 as soon as that gives every SIMD (1024 of them) one wave; smaller grids
+// split to fill the chip.  (the fold of S > 1 waves parks the value lists behind the logs: there is room for that with k <= 20 only)
+static int knn_s(const vcr_knn_args* a) {
   if (a->k > 20) return 1;
   if (a->waves == 1 || a->waves == 2 || a->waves == 4) return a->waves;
   const long groups = (long)((a->N + (a->C == 64 ? 31 : 15)) / (a->C == 64 ? 32 : 16)) * a->B;
   return groups >= 1024 ? 1 : groups >= 512 ? 2 : 4;
 }
-// 0: the tied rows go to a replay launch.  1: replayed by the workgroup that found them, row image in its LDS (N <= ~2400).
-// 2 (k > 20): likewise, row image in the workgroup's slot of tie_work (the caller gave vcr_knn_tie_slot_bytes(B, N) bytes of it).
-static int ties_inline(const vcr_knn_args* a) {
-  if (!a->tie_scratch) return 0;
-  if (a->C == 64 ? !use_col16(a) : knn_s(a) != 1) return 0;
-  if (inline_tie_offset(knn_log_bytes(a), a->N) + (1 + BLK_TIES) * 4 <= INLINE_TIE_MAX_LDS) return 1;
-  if (a->k <= 20) return 0;                              // (the slot form is compiled into the k > 20 kernels only)
-  const size_t slots = vcr_knn_tie_slot_bytes(a->B, a->N);
-  return (slots && a->tie_work && a->tie_work_bytes >= slots && !((uintptr_t)a->tie_work & 15)) ? 2 : 0;
-}
-static size_t knn_lds_bytes(const vcr_knn_args* a, int inl) {
-  return inl ? inline_tie_offset(knn_log_bytes(a), inl == 2 ? 0 : a->N) + (1 + BLK_TIES) * 4 : knn_log_bytes(a);
-}
-extern "C" int vcr_knn_ties_inline(const vcr_knn_args* ua) {
-  vcr_knn_args na;
-  const vcr_knn_args* a = &na;
-  return (knn_take(ua, &na) == 0 && a->x && a->idx && a->B > 0 && a->N > 0 && a->k > 0 && a->k <= 62 && (a->C == 64 || a->C == 4) && ties_inline(a)) ? 1 : 0;
-}
-
-// Feature-space (a64: C == 64) and Cartesian (a3: C == 4) kNN of the same pass as one launch (see knn_pair_kernel) when
-// both are in the one-list-per-query regime the path runs in (k <= 20, >= 1024 query groups each); any other shape
-// simply makes the two self-contained calls.  Tie handling as in vcr_knn_f32 (tie_defer honoured; a
-// replay that is not deferred serves both launches at once).
 // the ordered search's inputs are all there and the cloud is small enough for the wave's tile mask (256 tiles of 16 ranks)
 // (vcr_knn_order_f32 writes the ranked rows and the centroids at pitch C: a padded x keeps the plain scan)
 static bool knn_ordered(const vcr_knn_args* a) {
@@ -1712,159 +1655,206 @@ static bool knn_ordered(const vcr_knn_args* a) {
          a->ldx == a->C &&
          !(((uintptr_t)a->xp | (uintptr_t)a->cen) & 15);
 }
-extern "C" int vcr_knn_pair_f32(const vcr_knn_args* u64, const vcr_knn_args* u3, vcr_stream_t stream) {
-  vcr_knn_args n64_, n3_;
-  if (knn_take(u64, &n64_) || knn_take(u3, &n3_)) return VCR_EINVAL;
-  const vcr_knn_args *a64 = &n64_, *a3 = &n3_;
-  vcr_stream_scope scope_(stream);
-  if (!a64->x || !a3->x || !a64->idx || !a3->idx || a64->C != 64 || a3->C != 4) return VCR_EINVAL;
-  const bool col16 = use_col16(a64);
-  const bool fusable = a64->k == a3->k && (a64->k <= 20 || (col16 && a64->k <= 40)) &&      // (k > 20: the 16-query bodies only)
-                       (a64->waves == 0 || a64->waves == 1 || a64->waves == 8) && a3->waves == 0 &&
-                       (long)((a64->N + (col16 ? 15 : 31)) / (col16 ? 16 : 32)) * a64->B >= 1024 && (long)((a3->N + 15) / 16) * a3->B >= 1024 &&
-                       (a64->tie_scratch != nullptr) == (a3->tie_scratch != nullptr) && a64->tie_defer == a3->tie_defer;
-  // small grids: the candidate-split kernels of both searches as one launch (k <= 20, automatic kernel choice)
-  const bool small = !fusable && a64->k == a3->k && a64->k <= 20 && a64->waves == 0 && a3->waves == 0 && !col16 &&
-                     (a64->tie_scratch != nullptr) == (a3->tie_scratch != nullptr) && a64->tie_defer == a3->tie_defer &&
-                     a64->B > 0 && a3->B > 0 && a64->N > 0 && a3->N > 0 && a64->k > 0 && a64->k + 1 <= a64->N && a3->k + 1 <= a3->N &&
-                     a64->N <= KNN_MAX_N && a3->N <= KNN_MAX_N && !knn_rows_overflow(a64) && !knn_rows_overflow(a3) && a64->sq && a64->ldx >= 64 && !(a64->ldx & 3) && a3->ldx >= 4 && !(a3->ldx & 3) &&
-                     !(a64->tie_scratch && (a64->tie_cap < 1 || a3->tie_cap < 1)) && !tie_work_missing(a64) && !tie_work_missing(a3) &&
-                     knn_s(a64) != 1;                     // (an unsplit feature-space search on a small grid: the separate launches)
-  if (small) {
-    hipStream_t s = (hipStream_t)stream;
-    for (const vcr_knn_args* a : {a64, a3})
-      if (a->tie_scratch && !a->tie_zeroed) {
-        const int e = zero_count(a->tie_scratch, s);
-        if (e != 0) return e;
-      }
-    const int S64 = knn_s(a64), S3 = knn_s(a3);
-    const int gx64 = (a64->N + 32 * (4 / S64) - 1) / (32 * (4 / S64)), gx3 = (a3->N + 16 * (4 / S3) - 1) / (16 * (4 / S3));
-    const int n64 = gx64 * a64->B, n3 = gx3 * a3->B;
-    vcr_knn_args k64 = *a64, k3 = *a3;
-    k64.tie_inline = 0; k3.tie_inline = ties_inline(a3);               // (only an unsplit Cartesian search replays in place)
-    const size_t lds64 = (size_t)4 * 2 * (pend_of<GeomMfma, 22>() + 1) * 32 * 4;
-    const size_t lds3 = knn_lds_bytes(a3, k3.tie_inline), lds = lds64 > lds3 ? lds64 : lds3;
-    const dim3 grid(n64 + n3);
-    int rc = VCR_EUNSUPPORTED;
-#define VCR_KPS(A, B_) rc = launch<knn_pair_small_kernel<22, A, B_>>(grid, dim3(256), lds, s, k64, k3, n64, gx64, gx3)
-    if (S64 == 4) { if (S3 == 4) VCR_KPS(4, 4); else if (S3 == 2) VCR_KPS(4, 2); else VCR_KPS(4, 1); }
-    else if (S64 == 2) { if (S3 == 4) VCR_KPS(2, 4); else if (S3 == 2) VCR_KPS(2, 2); else VCR_KPS(2, 1); }
-#undef VCR_KPS
-    if (rc == 0 && a64->tie_scratch && !a64->tie_defer) rc = vcr_knn_ties_f32(a64, k3.tie_inline ? nullptr : a3, stream);
-    return rc;
+
+namespace {
+// How one search runs.  knn_plan() decides it from the search's arguments, and it is the only place that does: every entry
+// point below launches what the plans of its searches say.
+enum class KnnBody {
+  none,      // the arguments name no form (waves or C out of range)
+  mfma32,    // knn64_body (C == 64): 32-query waves on 32x32x2 MFMAs, S waves splitting a query group's candidates
+  col16,     // knn64c_body: 16-query waves on 16x16x4 MFMAs, four unsplit waves (C == 64: knn64c_kernel, C == 4: knn3c_kernel)
+  quad,      // knn3_body (C == 4, S = 2 / 4): DPP quads on the VALU, 16 queries a wave
+};
+struct KnnPlan {
+  vcr_knn_args a;            // what the kernels get: the caller's arguments with tie_inline set, perm cleared unless ord
+  KnnBody body;
+  int KS, S;                 // value lists of k + 2 entries rounded up to 22 / 42 / 64; waves sharing one group of queries
+  bool xt, ord;              // the 16-query feature-space waves read xt; the ordered inputs are complete (knn_ordered)
+  long groups;               // groups of queries of the form's wave size, all clouds: what the form was chosen by
+  dim3 grid, block; size_t lds;
+  bool zero, replay;         // the tie counter is zeroed first; a replay launch follows the search (owed, not deferred)
+};
+}  // namespace
+
+// Returns the first thing wrong with the arguments (VCR_OK: none).  The form is chosen even for invalid arguments when waves and
+// C name one: vcr_knn_pair_f32 decides between one launch and two before it reports which search is at fault.
+static int knn_plan(const vcr_knn_args& a, KnnPlan* p) {
+  *p = KnnPlan{a};
+  const bool waves_ok = a.waves == 0 || a.waves == 1 || a.waves == 2 || a.waves == 4 || a.waves == 8, c_ok = a.C == 64 || a.C == 4;
+  int e = VCR_OK;
+  if (!a.x || !a.idx || a.B <= 0 || a.N <= 0 || a.k <= 0 || a.k + 1 > a.N) e = VCR_EINVAL;
+  else if (a.k > 62 || a.N > KNN_MAX_N || knn_rows_overflow(&a)) e = VCR_EUNSUPPORTED;   // limits of this library (see vcr_hip.h)
+  else if (!waves_ok) e = VCR_EINVAL;
+  else if (!c_ok) e = VCR_EUNSUPPORTED;
+  if (!waves_ok || !c_ok) return e;
+  const bool k20 = a.k <= 20;
+  p->KS = k20 ? 22 : a.k <= 40 ? 42 : 64;               // one entry more than topk(k + 1): exposes boundary ties
+  const bool c16 = a.C == 64 && use_col16(&a);
+  p->S = c16 ? 1 : knn_s(&a);
+  p->body = c16 || (a.C == 4 && p->S == 1) ? KnnBody::col16 : a.C == 64 ? KnnBody::mfma32 : KnnBody::quad;
+  const int W = p->body == KnnBody::mfma32 && !k20 ? 2 : 4, QW = p->body == KnnBody::mfma32 ? 32 : 16;   // waves x queries
+  const long QB = (long)QW * (W / p->S);                 // queries of a workgroup
+  p->grid = dim3((unsigned)(((long)a.N + QB - 1) / QB), (unsigned)a.B);
+  p->block = dim3(64 * W);
+  p->groups = ((long)a.N + QW - 1) / QW * a.B;
+  p->xt = p->body == KnnBody::col16 && a.C == 64 && a.xt;
+  p->ord = knn_ordered(&a);
+  if (!p->ord) p->a.perm = nullptr;                      // (incomplete ordered inputs: the search runs the plain way)
+  // In-launch tie replay (col16 only: workgroups of four waves of 16 queries, see replay_block_ties).  0: the tied rows go to a
+  // replay launch.  1: replayed by the workgroup that found them, row image in its LDS beside nothing else in <= 40 KB (N <= ~2400).
+  // 2 (k > 20): likewise, row image in the workgroup's slot of tie_work (the caller gave vcr_knn_tie_slot_bytes(B, N) bytes of it;
+  // the slot form is compiled into the k > 20 kernels only).
+  int inl = 0;
+  if (p->body == KnnBody::col16) {
+    const size_t log = (size_t)4 * 2 * ((k20 ? pend_of<GeomCol16, 22>() : pend_of<GeomCol16, 42>()) + 4) * 16 * 4;   // the four logs
+    const size_t slots = vcr_knn_tie_slot_bytes(a.B, a.N);
+    if (a.tie_scratch && inline_tie_offset(log, a.N) + (1 + BLK_TIES) * 4 <= INLINE_TIE_MAX_LDS) inl = 1;
+    else if (a.tie_scratch && !k20 && slots && a.tie_work && a.tie_work_bytes >= slots && !((uintptr_t)a.tie_work & 15)) inl = 2;
+    p->lds = inl ? inline_tie_offset(log, inl == 2 ? 0 : a.N) + (1 + BLK_TIES) * 4 : log;
+  } else if (p->body == KnnBody::mfma32) {
+    p->lds = (size_t)W * 2 * ((k20 ? pend_of<GeomMfma, 22>() : pend_of<GeomMfma, 42>()) + 1) * 32 * 4;
+  } else {
+    p->lds = (size_t)4 * 2 * (pend_of<GeomQuad, 22>() + 1) * 16 * 4;   // (S > 1: k <= 20)
   }
-  if (!fusable) {
-    const int rc = vcr_knn_f32(a3, stream);
-    return rc ? rc : vcr_knn_f32(a64, stream);
-  }
-  for (const vcr_knn_args* a : {a64, a3}) {
-    if (a->B <= 0 || a->N <= 0 || a->k <= 0 || a->k + 1 > a->N || a->ldx < a->C || (a->ldx & 3)) return VCR_EINVAL;
-    if (a->N > KNN_MAX_N || knn_rows_overflow(a)) return VCR_EUNSUPPORTED;
-    if (a->tie_scratch && a->tie_cap < 1) return VCR_EINVAL;
-    if (tie_work_missing(a)) return VCR_EUNSUPPORTED;
-  }
-  if (!a64->sq) return VCR_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  for (const vcr_knn_args* a : {a64, a3})
-    if (a->tie_scratch && !a->tie_zeroed) {
-      const int e = zero_count(a->tie_scratch, s);
-      if (e != 0) return e;
-    }
-  const int gx64 = col16 ? (a64->N + 63) / 64 : (a64->N + 127) / 128, gx3 = (a3->N + 63) / 64;   // 4 waves x 16 (or 32) queries
-  const int n64 = gx64 * a64->B, n3 = gx3 * a3->B;
-  vcr_knn_args k64 = *a64, k3 = *a3;                     // (tie_inline is the library's own field)
-  k64.tie_inline = col16 ? ties_inline(a64) : 0; k3.tie_inline = ties_inline(a3);
-  if (!knn_ordered(a64)) k64.perm = nullptr;             // (incomplete ordered inputs: that search runs the plain way)
-  if (!knn_ordered(a3)) k3.perm = nullptr;
-  const size_t lds64 = col16 ? knn_lds_bytes(a64, k64.tie_inline) : (size_t)4 * 2 * (pend_of<GeomMfma, 22>() + 1) * 32 * 4;
-  const size_t lds3 = knn_lds_bytes(a3, k3.tie_inline), lds = lds64 > lds3 ? lds64 : lds3;
-  const dim3 grid(n64 + n3);
-  int rc;
-  if (!col16) rc = launch<knn_pair_kernel<22, false>>(grid, dim3(256), lds, s, k64, k3, n64, gx64, gx3);
-  else if ((knn_ordered(a64) || knn_ordered(a3)) && a64->xt)           // searches over the ranked rows (see vcr_knn_args.perm)
-    rc = a64->k <= 20 ? launch<knn_pair_kernel<22, true, true, true>>(grid, dim3(256), lds, s, k64, k3, n64, gx64, gx3)
-                      : launch<knn_pair_kernel<42, true, true, true>>(grid, dim3(256), lds, s, k64, k3, n64, gx64, gx3);
-  else if (a64->k <= 20) rc = a64->xt ? launch<knn_pair_kernel<22, true, true>>(grid, dim3(256), lds, s, k64, k3, n64, gx64, gx3)
-                                      : launch<knn_pair_kernel<22, true>>(grid, dim3(256), lds, s, k64, k3, n64, gx64, gx3);
-  else rc = a64->xt ? launch<knn_pair_kernel<42, true, true>>(grid, dim3(256), lds, s, k64, k3, n64, gx64, gx3)
-                    : launch<knn_pair_kernel<42, true>>(grid, dim3(256), lds, s, k64, k3, n64, gx64, gx3);
-  // whatever was not replayed inside the launch: one replay launch, now or (tie_defer) when the caller asks for it
-  if (rc == 0 && a64->tie_scratch && !a64->tie_defer) {
-    if (!k64.tie_inline && !k3.tie_inline) rc = vcr_knn_ties_f32(a64, a3, stream);
-    else if (!k64.tie_inline) rc = vcr_knn_ties_f32(a64, nullptr, stream);
-    else if (!k3.tie_inline) rc = vcr_knn_ties_f32(a3, nullptr, stream);
-  }
-  return rc;
+  p->a.tie_inline = inl;
+  p->zero = a.tie_scratch && !a.tie_zeroed;
+  p->replay = a.tie_scratch && !a.tie_defer && !inl;
+  if (e) return e;
+  if ((a.C == 64 ? (!a.sq || a.ldx < 64 || (a.ldx & 3)) : (a.ldx < 4 || (a.ldx & 3))) || (a.tie_scratch && a.tie_cap < 1)) return VCR_EINVAL;
+  // a replay is owed (now or deferred) but the rows need global scratch that the caller did not provide: refuse loudly rather
+  // than skip the replay silently
+  const size_t need = vcr_knn_tie_work_bytes(a.N);
+  if (a.tie_scratch && inl != 2 && need && (!a.tie_work || a.tie_work_bytes < need || ((uintptr_t)a.tie_work & 15))) return VCR_EUNSUPPORTED;
+  return VCR_OK;
+}
+
+static int zero_ties(const KnnPlan& p, hipStream_t s) { return p.zero ? zero_count(p.a.tie_scratch, s) : VCR_OK; }
+// rows with an exact tie at the (k+1)-th value: replay libstdc++'s selection on them (knn_tiebreak_kernel); b: a second search or NULL
+static int replay(const vcr_knn_args& a, const vcr_knn_args* b, hipStream_t s) {
+  const size_t la = tiebreak_launch_lds(a.N), lb = b ? tiebreak_launch_lds(b->N) : 0, lds = la > lb ? la : lb;
+  if (b) return launch<knn_tiebreak2_kernel>(dim3(TB_BLOCKS, 2), dim3(256), lds, s, a, *b);
+  return launch<knn_tiebreak_kernel>(dim3(TB_BLOCKS), dim3(256), lds, s, a);
+}
+
+// one search: zero the tie counter, search, replay
+static int knn_run(const KnnPlan& p, hipStream_t s) {
+  int rc = zero_ties(p, s);
+  if (rc) return rc;
+#define VCR_K(...) rc = launch<__VA_ARGS__>(p.grid, p.block, p.lds, s, p.a)
+  if (p.body == KnnBody::col16 && p.a.C == 4) { if (p.KS == 22) VCR_K(knn3c_kernel<22, 4>); else if (p.KS == 42) VCR_K(knn3c_kernel<42, 4>); else VCR_K(knn3c_kernel<64, 4>); }
+  else if (p.body == KnnBody::col16 && p.xt) { if (p.KS == 22) VCR_K(knn64c_kernel<22, 4, true>); else if (p.KS == 42) VCR_K(knn64c_kernel<42, 4, true>); else VCR_K(knn64c_kernel<64, 4, true>); }
+  else if (p.body == KnnBody::col16) { if (p.KS == 22) VCR_K(knn64c_kernel<22, 4, false>); else if (p.KS == 42) VCR_K(knn64c_kernel<42, 4, false>); else VCR_K(knn64c_kernel<64, 4, false>); }
+  else if (p.body == KnnBody::mfma32) { if (p.KS == 42) VCR_K(knn64_kernel<42, 1, 2>); else if (p.S == 1) VCR_K(knn64_kernel<22, 1, 4>); else if (p.S == 2) VCR_K(knn64_kernel<22, 2, 4>); else VCR_K(knn64_kernel<22, 4, 4>); }
+  else if (p.S == 2) VCR_K(knn3_kernel<22, 2>);
+  else VCR_K(knn3_kernel<22, 4>);
+#undef VCR_K
+  return rc ? rc : p.replay ? replay(p.a, nullptr, s) : VCR_OK;
 }
 
 extern "C" int vcr_knn_f32(const vcr_knn_args* ua, vcr_stream_t stream) {
-  vcr_knn_args na;
-  if (knn_take(ua, &na)) return VCR_EINVAL;
-  const vcr_knn_args* a = &na;
+  vcr_knn_args a;
+  if (knn_take(ua, &a)) return VCR_EINVAL;
   vcr_stream_scope scope_(stream);
-  if (!a->x || !a->idx) return VCR_EINVAL;
-  if (a->B <= 0 || a->N <= 0 || a->k <= 0 || a->k + 1 > a->N) return VCR_EINVAL;
-  if (a->k > 62 || a->N > KNN_MAX_N || knn_rows_overflow(a)) return VCR_EUNSUPPORTED;   // limits of this library, not of the operation (see vcr_hip.h):
-                                                            // the tie replay keeps topk(k + 1)'s heap in the 64 lanes of a wave
-  if (a->waves != 0 && a->waves != 1 && a->waves != 2 && a->waves != 4 && a->waves != 8) return VCR_EINVAL;
-  if (a->C != 64 && a->C != 4) return VCR_EUNSUPPORTED;
-  if (a->C == 64 ? (!a->sq || a->ldx < 64 || (a->ldx & 3)) : (a->ldx < 4 || (a->ldx & 3))) return VCR_EINVAL;
+  KnnPlan p;
+  const int e = knn_plan(a, &p);
+  return e ? e : knn_run(p, (hipStream_t)stream);
+}
+
+extern "C" int vcr_knn_ties_inline(const vcr_knn_args* ua) {
+  vcr_knn_args a;
+  KnnPlan p;
+  return (knn_take(ua, &a) == 0 && knn_plan(a, &p) == VCR_OK && p.a.tie_inline) ? 1 : 0;
+}
+
+extern "C" int vcr_knn_ties_f32(const vcr_knn_args* ua, const vcr_knn_args* ub, vcr_stream_t stream) {
+  vcr_knn_args a, b;
+  if (knn_take(ua, &a) || (ub && knn_take(ub, &b))) return VCR_EINVAL;
+  vcr_stream_scope scope_(stream);
+  KnnPlan pa, pb;
+  int e = knn_plan(a, &pa);
+  if (!e && ub) e = knn_plan(b, &pb);
+  if (e) return e;
+  if (!a.tie_scratch || (ub && !b.tie_scratch)) return VCR_EINVAL;
+  return replay(pa.a, ub ? &pb.a : nullptr, (hipStream_t)stream);
+}
+
+// Feature-space (a64: C == 64) and Cartesian (a3: C == 4) kNN of the same pass as ONE launch, decided on their standalone plans,
+// when both have the same k, the automatic Cartesian form (a3.waves == 0) and the same tie handling (tie_scratch or not, tie_defer):
+// fused (knn_pair_kernel) when both plans are unsplit four-wave forms with lists of 22 / 42 and >= 1024 query groups each (the
+// regime of the path; with 16-query waves the one form that reads the ordered inputs), small (knn_pair_small_kernel) when the
+// arguments are valid and the feature-space search splits its candidates by its own choice (small grids).  Anything else: the two
+// vcr_knn_f32 calls.  A replay that is not deferred serves both searches at once.
+enum class PairForm { separate, fused, small };
+static PairForm pair_form(const KnnPlan& p64, const KnnPlan& p3, bool valid) {
+  const vcr_knn_args &a64 = p64.a, &a3 = p3.a;
+  if (a64.k != a3.k || a3.waves != 0 || (a64.tie_scratch != nullptr) != (a3.tie_scratch != nullptr) || a64.tie_defer != a3.tie_defer)
+    return PairForm::separate;
+  auto unsplit4 = [](const KnnPlan& p) { return p.body == KnnBody::col16 || (p.body == KnnBody::mfma32 && p.S == 1 && p.block.x == 256); };
+  if (unsplit4(p64) && unsplit4(p3) && p64.KS <= 42 && p64.groups >= 1024 && p3.groups >= 1024) return PairForm::fused;
+  if (valid && a64.waves == 0 && p64.body == KnnBody::mfma32 && p64.S > 1) return PairForm::small;
+  return PairForm::separate;
+}
+// both plans, and the pair's own requirement: which search is which
+static int pair_plans(const vcr_knn_args& a64, const vcr_knn_args& a3, KnnPlan* p64, KnnPlan* p3, int* e64, int* e3) {
+  if (!a64.x || !a3.x || !a64.idx || !a3.idx || a64.C != 64 || a3.C != 4) return VCR_EINVAL;
+  *e64 = knn_plan(a64, p64);
+  *e3 = knn_plan(a3, p3);
+  return VCR_OK;
+}
+
+extern "C" int vcr_knn_pair_f32(const vcr_knn_args* u64, const vcr_knn_args* u3, vcr_stream_t stream) {
+  vcr_knn_args a64, a3;
+  if (knn_take(u64, &a64) || knn_take(u3, &a3)) return VCR_EINVAL;
+  vcr_stream_scope scope_(stream);
+  KnnPlan p64, p3;
+  int e64 = VCR_OK, e3 = VCR_OK;
+  if (pair_plans(a64, a3, &p64, &p3, &e64, &e3)) return VCR_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  if (a->tie_scratch) {
-    if (a->tie_cap < 1) return VCR_EINVAL;
-    if (tie_work_missing(a)) return VCR_EUNSUPPORTED;     // refuse loudly rather than skip the replay silently
-    if (!a->tie_zeroed) {
-      const int e = zero_count(a->tie_scratch, s);
-      if (e != 0) return e;
-    }
+  const PairForm form = pair_form(p64, p3, !e64 && !e3);
+  if (form == PairForm::separate) {
+    const int rc = e3 ? e3 : knn_run(p3, s);
+    return rc ? rc : e64 ? e64 : knn_run(p64, s);
   }
-  int rc = VCR_EUNSUPPORTED;
-  const bool k20 = a->k <= 20;                           // list of k+2 entries (one more than topk(k+1): exposes boundary ties)
-  // S waves of a workgroup share one group of queries and split its candidates.  The selection work grows with the
-  // number of lists (S per query), and measured on MI355X a second wave per SIMD bought with S = 2 only breaks even, so
-  // S stays 1 as soon as that gives every SIMD (1024 of them) one wave; smaller grids split to fill the chip.
-  // (the fold of S > 1 waves parks the value lists behind the logs: there is room for that with k <= 20 only)
-  auto pick_s = [&](long) { return knn_s(a); };
-  vcr_knn_args ka = *a;                                  // (tie_inline is the library's own field)
-  const int inl = ties_inline(a);
-  ka.tie_inline = inl;
-  if (a->C == 64 && use_col16(a)) {
-    // the half-size-wave kernel (see use_col16)
-    if (!a->sq || a->ldx < 64 || (a->ldx & 3)) return VCR_EINVAL;
-    const dim3 grid((a->N + 63) / 64, a->B);
-    const size_t lds = knn_lds_bytes(a, inl);
-    const bool k40 = a->k <= 40;                         // lists of k + 2: 22 / 42 / 64 entries
-    if (a->xt) rc = k20 ? launch<knn64c_kernel<22, 4, true>>(grid, dim3(256), lds, s, ka)
-                  : k40 ? launch<knn64c_kernel<42, 4, true>>(grid, dim3(256), lds, s, ka)
-                        : launch<knn64c_kernel<64, 4, true>>(grid, dim3(256), lds, s, ka);
-    else rc = k20 ? launch<knn64c_kernel<22, 4, false>>(grid, dim3(256), lds, s, ka)
-              : k40 ? launch<knn64c_kernel<42, 4, false>>(grid, dim3(256), lds, s, ka)
-                    : launch<knn64c_kernel<64, 4, false>>(grid, dim3(256), lds, s, ka);
-  } else if (a->C == 64) {
-    if (!a->sq || a->ldx < 64 || (a->ldx & 3)) return VCR_EINVAL;
-    const int S = pick_s((long)((a->N + 31) / 32) * a->B), W = k20 ? 4 : 2;
-    const dim3 grid((a->N + 32 * (W / S) - 1) / (32 * (W / S)), a->B);
-    const size_t lds = (size_t)W * 2 * ((k20 ? pend_of<GeomMfma, 22>() : pend_of<GeomMfma, 42>()) + 1) * 32 * 4;
-    rc = !k20 ? launch<knn64_kernel<42, 1, 2>>(grid, dim3(128), lds, s, *a)
-         : S == 1 ? launch<knn64_kernel<22, 1, 4>>(grid, dim3(256), lds, s, *a)
-         : S == 2 ? launch<knn64_kernel<22, 2, 4>>(grid, dim3(256), lds, s, *a)
-                  : launch<knn64_kernel<22, 4, 4>>(grid, dim3(256), lds, s, *a);
-  } else if (a->C == 4) {
-    if (a->ldx < 4 || (a->ldx & 3)) return VCR_EINVAL;
-    const int S = pick_s((long)((a->N + 15) / 16) * a->B);
-    const dim3 grid((a->N + 16 * (4 / S) - 1) / (16 * (4 / S)), a->B);
-    const size_t lds = knn_lds_bytes(a, inl);
-    rc = a->k > 40 ? launch<knn3c_kernel<64, 4>>(grid, dim3(256), lds, s, ka)
-         : !k20 ? launch<knn3c_kernel<42, 4>>(grid, dim3(256), lds, s, ka)
-         : S == 1 ? launch<knn3c_kernel<22, 4>>(grid, dim3(256), lds, s, ka)
-         : S == 2 ? launch<knn3_kernel<22, 2>>(grid, dim3(256), lds, s, *a)
-                  : launch<knn3_kernel<22, 4>>(grid, dim3(256), lds, s, *a);
+  if (e64 || e3) return e64 ? e64 : e3;
+  int rc = zero_ties(p64, s);
+  if (!rc) rc = zero_ties(p3, s);
+  if (rc) return rc;
+  const int gx64 = (int)p64.grid.x, gx3 = (int)p3.grid.x, n64 = gx64 * a64.B;
+  const dim3 grid(n64 + gx3 * a3.B), block(256);
+  const size_t lds = p64.lds > p3.lds ? p64.lds : p3.lds;
+  const vcr_knn_args &k64 = p64.a, &k3 = p3.a;
+#define VCR_KP(...) rc = launch<__VA_ARGS__>(grid, block, lds, s, k64, k3, n64, gx64, gx3)
+  if (form == PairForm::small) {
+    if (p64.S == 4) { if (p3.S == 4) VCR_KP(knn_pair_small_kernel<22, 4, 4>); else if (p3.S == 2) VCR_KP(knn_pair_small_kernel<22, 4, 2>); else VCR_KP(knn_pair_small_kernel<22, 4, 1>); }
+    else { if (p3.S == 4) VCR_KP(knn_pair_small_kernel<22, 2, 4>); else if (p3.S == 2) VCR_KP(knn_pair_small_kernel<22, 2, 2>); else VCR_KP(knn_pair_small_kernel<22, 2, 1>); }
+  } else if (p64.body == KnnBody::mfma32) {
+    VCR_KP(knn_pair_kernel<22, false>);
+  } else if ((p64.ord || p3.ord) && p64.xt) {            // searches over the ranked rows (see vcr_knn_args.perm)
+    if (p64.KS == 22) VCR_KP(knn_pair_kernel<22, true, true, true>); else VCR_KP(knn_pair_kernel<42, true, true, true>);
+  } else if (p64.KS == 22) {
+    if (p64.xt) VCR_KP(knn_pair_kernel<22, true, true>); else VCR_KP(knn_pair_kernel<22, true>);
+  } else {
+    if (p64.xt) VCR_KP(knn_pair_kernel<42, true, true>); else VCR_KP(knn_pair_kernel<42, true>);
   }
-  if (rc != 0) return rc;
-  // rows with an exact tie at the (k+1)-th value: replay libstdc++'s selection on them (see knn_tiebreak_kernel)
-  const size_t tb_lds = tiebreak_launch_lds(a->N);
-  if (a->tie_scratch && !a->tie_defer && !inl) {         // (inl: the launch replayed its ties itself)
-    rc = launch<knn_tiebreak_kernel>(dim3(TB_BLOCKS), dim3(256), tb_lds, s, *a);
-  }
-  return rc;
+#undef VCR_KP
+  // whatever was not replayed inside the launch: one replay launch, now or (tie_defer) when the caller asks for it
+  if (rc || !(p64.replay || p3.replay)) return rc;
+  return p64.replay ? replay(p64.a, p3.replay ? &p3.a : nullptr, s) : replay(p3.a, nullptr, s);
+}
+
+// Host-only, library-internal (forward.hip): what the plans say of one search (b == NULL, as vcr_knn_f32 runs it) or of a pair (a64, a3
+// as vcr_knn_pair_f32 runs them).  ordered: the pair takes the one form that reads the ordered inputs (which do not change the form);
+// inline_a / inline_b: that search replays its tied rows inside its launch.
+extern "C" int vcr_knn_forms_(const vcr_knn_args* ua, const vcr_knn_args* ub, int* ordered, int* inline_a, int* inline_b) {
+  vcr_knn_args a, b;
+  if (knn_take(ua, &a) || (ub && knn_take(ub, &b))) return VCR_EINVAL;
+  KnnPlan pa, pb;
+  int ea = VCR_OK, eb = VCR_OK;
+  if (!ub) ea = knn_plan(a, &pa);
+  else if (pair_plans(a, b, &pa, &pb, &ea, &eb)) return VCR_EINVAL;
+  if (ea || eb) return ea ? ea : eb;
+  if (ordered) *ordered = ub && pair_form(pa, pb, true) == PairForm::fused && pa.body == KnnBody::col16 && pa.xt;
+  if (inline_a) *inline_a = pa.a.tie_inline != 0;
+  if (inline_b) *inline_b = ub && pb.a.tie_inline != 0;
+  return VCR_OK;
 }

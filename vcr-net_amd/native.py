@@ -400,21 +400,16 @@ def knn(x, sq, k, exact_ties=True, waves=0, tie_work=True, xt=None, tie_slots=Fa
     idx = torch.empty(B, N, k, dtype=torch.int32, device=x.device)
     ties = torch.empty(1 + B * N, dtype=torch.int32, device=x.device) if exact_ties else None   # room for every row
     a = KnnArgs(ptr(x), x.stride(1), ptr(sq), B, N, Cc, k, ptr(idx), ptr(ties), B * N if exact_ties else 0, waves)
-    L = lib()
-    L.vcr_knn_tie_work_bytes.restype, L.vcr_knn_tie_work_bytes.argtypes = C.c_size_t, [C.c_int]
-    need = L.vcr_knn_tie_work_bytes(N) if (exact_ties and tie_work) else 0
-    if exact_ties and tie_slots:
-        L.vcr_knn_tie_slot_bytes.restype, L.vcr_knn_tie_slot_bytes.argtypes = C.c_size_t, [C.c_int, C.c_int]
-        need = L.vcr_knn_tie_slot_bytes(B, N)
-    work = torch.empty(need, dtype=torch.uint8, device=x.device) if need else None            # long rows: replay scratch
-    a.tie_work, a.tie_work_bytes = ptr(work), need
+    keep = []                    # long rows: replay scratch
+    if exact_ties and (tie_work or tie_slots):
+        _tie_work(a, N, x.device, keep, slots_for=B if tie_slots else 0)
     a.xt = ptr(xt)               # the rows with their 16-channel groups transposed (pointwise(..., feat_t=)): same result
     call("vcr_knn_f32", a)
     return idx
 
 
 def _tie_work(a, N, device, keep, slots_for=0):
-    """Long rows (vcr_knn_tie_work_bytes(N) > 0, N > ~10 100): the replay's global scratch, as knn() provides it.
+    """Long rows (vcr_knn_tie_work_bytes(N) > 0, N > ~10 100): the replay's global scratch (knn(), knn_pair()).
     slots_for = B: vcr_knn_tie_slot_bytes(B, N) instead -- the launch replays its own ties (vcr_knn_args.tie_inline 2)."""
     L = lib()
     L.vcr_knn_tie_work_bytes.restype, L.vcr_knn_tie_work_bytes.argtypes = C.c_size_t, [C.c_int]
