@@ -18,6 +18,13 @@
  *     travel in the args structs (`variant`, `waves`), 0 = the automatic choice;
  *   - activations are fp32, point-major ("channels-last"): a [B,N,C] tensor is row-major with one
  *     row per point and an explicit row pitch `ld*` in floats.  Indices are int32.
+ *   - non-finite input: every index an entry point writes is in range whatever the values -- kNN:
+ *     [0, N) of the query's own cloud, a short list (NaN scores never qualify) padded with the query's own index;
+ *     rankselect: a permutation prefix of [0, n), compared in torch's order (NaN above +inf, -0 == +0, equal keys by
+ *     index); the pair-score arg-max: [0, n_str), torch.argmax's rule (the first NaN, else the first maximum; all -inf:
+ *     0); forced / reported selections: in range of their cloud.  rigid_svd writes an all-NaN pose when H or a mean is
+ *     non-finite, so a pair whose non-finite point reaches the solve comes back all NaN and the other pairs of the batch
+ *     are untouched.  The forwards take src and tgt of the same B and N.
  */
 #ifndef VCR_HIP_H
 #define VCR_HIP_H

@@ -415,7 +415,8 @@ __device__ __forceinline__ void finish(Selector<G, KS>& sel, const vcr_knn_args&
   // its sort (util.py:159 then drops that one and keeps the others): such a row is replayed like a boundary tie (best_shared
   // below; tiebreak_row sorts the kept entries the way ATen does).  Without tie_scratch: the first logged is dropped.
   // (Whether it is shared is read off the sorted value list: its two best entries are equal.)
-  const bool best_shared = sel.rank_value(0) == sel.rank_value(1);
+  // (-inf == -inf is no tie: a query with fewer than two finite scores -- its own coordinate non-finite -- has nothing to replay)
+  const bool best_shared = sel.rank_value(0) == sel.rank_value(1) && sel.rank_value(1) > VCR_NEG_INF;
   int imax = 0;
   float vmax = VCR_NEG_INF;
   if (perm) {
@@ -439,6 +440,9 @@ __device__ __forceinline__ void finish(Selector<G, KS>& sel, const vcr_knn_args&
     int32_t* o = a.idx + ((size_t)b * a.N + q) * a.k;
     for (int i = sel.sg; i < sel.cnt && i <= a.k; i += G::LPQ)
       if (i != imax) o[i - (i > imax ? 1 : 0)] = sel.li[i * G::COLS + sel.col];
+    // A short list -- NaN scores never pass the filter: the query's own coordinate is non-finite, or its cloud has fewer than
+    // k + 1 finite points -- leaves slots unwritten: they take the query's own index, so that every slot is a row of its cloud.
+    for (int i = min(sel.cnt, a.k + 1) - (sel.cnt > 0 ? 1 : 0) + sel.sg; i < a.k; i += G::LPQ) o[i] = q;
     if (sel.sg == 0 && ((vk1 == vk && vk1 > VCR_NEG_INF) || best_shared)) {
       if (blk_ties) {                                    // replayed by this very workgroup (replay_block_ties)
         const int pos = atomicAdd(&blk_ties[0], 1);
@@ -1531,7 +1535,8 @@ __device__ void tiebreak_row(const vcr_knn_args& a, int row, unsigned char* smem
         const float dot = fmaf(qv[2], cv[2], fmaf(qv[1], cv[1], qv[0] * cv[0]));
         d = (2.f * dot - cv[3]) - qv[3];
       }
-      val[j] = d; id[j] = j;
+      val[j] = d == d ? d : VCR_NEG_INF;                 // NaN (a non-finite point): below everything, as the main kernels filter it;
+      id[j] = j;                                         // the ports' stoppers and the block partition need a total order
     }
     __syncthreads();
     PairArr q{val, id};

@@ -81,7 +81,8 @@ __global__ __launch_bounds__(1024) void knn_morton_kernel(const float* xyz4, int
     for (int d = 0; d < 3; ++d) {
       const float ext = hi[d] - lo[d];
       const float u = ext > 0.f ? (v[d] - lo[d]) / ext : 0.f;
-      const unsigned qd = (unsigned)fminf(fmaxf(u * 1024.f, 0.f), 1023.f);
+      const float s = u * 1024.f;                            // NaN (a non-finite coordinate, or a box made non-finite by one): code 0
+      const unsigned qd = s >= 1023.f ? 1023u : s > 0.f ? (unsigned)s : 0u;
       code |= spread10(qd) << d;
     }
     return ((unsigned long long)code << 32) | (unsigned)i;
@@ -157,7 +158,8 @@ __global__ __launch_bounds__(256) void knn_rank_rows_kernel(vcr_knn_order_args a
     const float nmax = rows_max(valid ? v[3] : 0.f);
     if (lane == 0) {
       st4(a.cen4 + ((size_t)b * T + t) * 4, f32x4{c[0], c[1], c[2], c[0] * c[0] + c[1] * c[1] + c[2] * c[2]});
-      a.cen4_rad[(size_t)b * T + t] = __builtin_sqrtf(d2 * 1.00002f) * 1.000002f + 1e-30f;      // rounded UP: a bound
+      const float rad = __builtin_sqrtf(d2 * 1.00002f) * 1.000002f + 1e-30f;                     // rounded UP: a bound
+      a.cen4_rad[(size_t)b * T + t] = rad == rad ? rad : __builtin_huge_valf();               // a non-finite row: never pruned
       a.cen4_sqmax[(size_t)b * T + t] = nmax;
     }
   }
@@ -197,7 +199,8 @@ __global__ __launch_bounds__(256) void knn_rank_rows_kernel(vcr_knn_order_args a
   }
   if (lane == 0) {
     a.cen64_sq[(size_t)b * T + t] = cn;
-    a.cen64_rad[(size_t)b * T + t] = __builtin_sqrtf(d2 * 1.00002f) * 1.000002f + 1e-30f;
+    const float rad = __builtin_sqrtf(d2 * 1.00002f) * 1.000002f + 1e-30f;
+    a.cen64_rad[(size_t)b * T + t] = rad == rad ? rad : __builtin_huge_valf();
     a.cen64_sqmax[(size_t)b * T + t] = nmax;
   }
 }

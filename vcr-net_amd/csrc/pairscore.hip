@@ -23,6 +23,12 @@ namespace {
 
 constexpr float LOG2E = 1.4426950408889634f;
 
+// op 1's arg-max in torch.argmax's order: the first NaN wins, else the first maximum (an all -inf row: index 0, see the store)
+__device__ __forceinline__ bool argmax_before(float v, int i, float bv, int bi) {
+  const bool vn = v != v, bn = bv != bv;
+  return vn ? (!bn || i < bi) : (!bn && (v > bv || (v == bv && i < bi)));
+}
+
 // OT = owner tiles (of 32) per block.  Every block streams ALL streamed rows past its owners, so the L2 traffic per
 // MAC is 1/(32 OT): with one tile the kernel is L2-bandwidth-bound (16 flop/B -> ~6 TB/s at 96 TFLOP/s measured);
 // two tiles, shared by 8 waves, halve that.  Each streamed fragment (MFMA A operand, registers) is then used
@@ -163,7 +169,7 @@ __global__ __launch_bounds__(128 * OT * 2, (OT == 1 ? 2 : 1)) void pairscore_ker
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int j = tile * 32 + acc_row(r, half);
-          if (sc16[r] > best[ot]) { best[ot] = sc16[r]; bidx[ot] = j; }
+          if (sc16[r] > best[ot] || (sc16[r] != sc16[r] && best[ot] == best[ot])) { best[ot] = sc16[r]; bidx[ot] = j; }   // (j ascends)
         }
       }
       mt = fmaxf(mt, xhalf(mt));
@@ -216,7 +222,7 @@ __global__ __launch_bounds__(128 * OT * 2, (OT == 1 ? 2 : 1)) void pairscore_ker
       if (OP == 1) {
         const float ob = xhalf(best[ot]);
         const int oi = __shfl_xor(bidx[ot], 32, 64);
-        if (ob > best[ot] || (ob == best[ot] && oi < bidx[ot])) { best[ot] = ob; bidx[ot] = oi; }
+        if (argmax_before(ob, oi, best[ot], bidx[ot])) { best[ot] = ob; bidx[ot] = oi; }
       }
       if (half == 0) {
         g[0] = m[ot]; g[1] = l[ot];
@@ -248,7 +254,7 @@ __global__ __launch_bounds__(128 * OT * 2, (OT == 1 ? 2 : 1)) void pairscore_ker
       if (OP == 0) { X = fmaf(g[2], a, X); Y = fmaf(g[3], a, Y); Z = fmaf(g[4], a, Z); }
       else {
         const int gi = __float_as_int(g[3]);
-        if (g[2] > Bv || (g[2] == Bv && gi < Bi)) { Bv = g[2]; Bi = gi; }
+        if (argmax_before(g[2], gi, Bv, Bi)) { Bv = g[2]; Bi = gi; }
       }
     }
     if (OP == 0) {
@@ -262,7 +268,7 @@ __global__ __launch_bounds__(128 * OT * 2, (OT == 1 ? 2 : 1)) void pairscore_ker
     } else {
       float* st = nsplit > 1 ? p.split_work + (size_t)sp * p.nbatch * p.n_own * 2 : p.stat2;
       st[orow * 2] = M; st[orow * 2 + 1] = L;
-      if (p.argmax) p.argmax[orow] = Bi;
+      if (p.argmax) p.argmax[orow] = Bi < p.n_str ? Bi : 0;     // nothing beat -inf: every score is -inf, the first wins
     }
   }
 }

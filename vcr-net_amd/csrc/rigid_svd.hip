@@ -168,6 +168,13 @@ __global__ __launch_bounds__(256) void rigid_svd_kernel(vcr_rigid_svd_args p) {
   if (t == 0) {
     double R[9];
     svd3_finish(A, V, R);
+    // a non-finite correspondence or point (the reference's torch.svd raises on it): the whole pose is NaN, stated here
+    // rather than left to the sweeps, whose fmax-style tests can squash a NaN
+    bool finite = true;
+    for (int e = 0; e < 9; ++e) finite = finite && __builtin_isfinite(H[e]);
+    for (int c = 0; c < 6; ++c) finite = finite && __builtin_isfinite(mean[c]);
+    if (!finite)
+      for (int e = 0; e < 9; ++e) R[e] = __builtin_nan("");
     float* Ro = p.R + (size_t)b * 9;
     float* to = p.t + (size_t)b * 3;
     float Rf[9], tf[3];

@@ -549,6 +549,7 @@ class VCRNet(nn.Module):
         if self.training or torch.is_grad_enabled():
             raise native.VcrHipError("inference only: call .eval() and wrap in torch.no_grad() "
                                      "(model/vcrnet_model.py:546); backward kernels are out of scope")
+        _check_shapes(src, tgt)
 
     # -- forward ------------------------------------------------------------------------------------------------
     def forward(self, *input):
@@ -588,6 +589,7 @@ class VCRNet(nn.Module):
             return self._forward_fused_on(src, tgt, trace, want_emb, iters, force, want_selections, iter_api)
 
     def _forward_fused_on(self, src, tgt, trace, want_emb, iters, force, want_selections, iter_api):
+        _check_shapes(src, tgt)
         self._pack()
         B, _, N = src.shape
         dev = native.same_device(src, tgt, next(iter(self._tensors().values())))
@@ -656,6 +658,16 @@ class VCRNet(nn.Module):
         if not self.fused_supported():
             return None
         return self._forward_fused(src, tgt, trace=self.launch_trace, iters=int(iters), iter_api=True)
+
+
+def _check_shapes(src, tgt):
+    """src and tgt must both be [B, 3, N] with the same B and N: the device reads B * 3 * N floats of each (unequal cloud
+    sizes are not served)."""
+    if src.dim() != 3 or tgt.dim() != 3 or src.shape[1] != 3 or tgt.shape[1] != 3:
+        raise native.VcrHipError(f"src and tgt must be [B, 3, N] point clouds, got {tuple(src.shape)} and {tuple(tgt.shape)}")
+    if src.shape != tgt.shape:
+        raise native.VcrHipError(f"tgt must have the same B and N as src, got src {tuple(src.shape)} and tgt {tuple(tgt.shape)}"
+                                 " (clouds of unequal size are not supported)")
 
 
 class DCP(VCRNet):

@@ -373,6 +373,13 @@ def _f32(*shape, device):
     return torch.empty(*shape, dtype=torch.float32, device=device)
 
 
+def _i32(*shape, device, prefill=None):
+    """An int32 output buffer; prefill = a value it holds before the launch (the tests' sentinel for slots left unwritten)."""
+    if prefill is None:
+        return torch.empty(*shape, dtype=torch.int32, device=device)
+    return torch.full(shape, prefill, dtype=torch.int32, device=device)
+
+
 @_guarded
 def pointwise(x_cf, w1, b1, w2, b2, pq_w=None, pq_b=None, feat_t=None):
     """conv1_lpd + conv2_lpd (+ ReLU) -> (xyz4, feat64, sq64); with pq_w [256,64] / pq_b [256] also the P | Q projection
@@ -392,12 +399,13 @@ def pointwise(x_cf, w1, b1, w2, b2, pq_w=None, pq_b=None, feat_t=None):
 
 
 @_guarded
-def knn(x, sq, k, exact_ties=True, waves=0, tie_work=True, xt=None, tie_slots=False):
+def knn(x, sq, k, exact_ties=True, waves=0, tie_work=True, xt=None, tie_slots=False, prefill=None):
     """x [B,N,C] rows (C = 64 with sq [B,N], or C = 4 xyz4 rows) -> int32 idx [B,N,k].  exact_ties: rows whose
     (k+1)-th and (k+2)-th distances are equal get Tensor.topk's (libstdc++'s) pick instead of the lower index.
-    tie_slots: give the launch vcr_knn_tie_slot_bytes(B, N) of scratch -- it then replays its tied rows itself."""
+    tie_slots: give the launch vcr_knn_tie_slot_bytes(B, N) of scratch -- it then replays its tied rows itself.
+    prefill: a value idx holds before the launch (torch.empty otherwise)."""
     B, N, Cc = x.shape
-    idx = torch.empty(B, N, k, dtype=torch.int32, device=x.device)
+    idx = _i32(B, N, k, device=x.device, prefill=prefill)
     ties = torch.empty(1 + B * N, dtype=torch.int32, device=x.device) if exact_ties else None   # room for every row
     a = KnnArgs(ptr(x), x.stride(1), ptr(sq), B, N, Cc, k, ptr(idx), ptr(ties), B * N if exact_ties else 0, waves)
     keep = []                    # long rows: replay scratch
@@ -422,15 +430,16 @@ def _tie_work(a, N, device, keep, slots_for=0):
 
 
 @_guarded
-def knn_pair(feat, sq, xyz4, k, xt=None, order=None, tie_slots=False):
+def knn_pair(feat, sq, xyz4, k, xt=None, order=None, tie_slots=False, prefill=None):
     """vcr_knn_pair_f32: the feature-space (feat [B,N,64], sq [B,N]) and the Cartesian (xyz4 [B,N,4]) kNN in one launch
     -> (idx_feat, idx_xyz), tie replay included.  order = knn_order()'s dict: the ordered search (vcr_knn_args.perm).
-    tie_slots: per-workgroup replay slots (vcr_knn_tie_slot_bytes) -- tied rows are replayed inside the launch."""
+    tie_slots: per-workgroup replay slots (vcr_knn_tie_slot_bytes) -- tied rows are replayed inside the launch.
+    prefill: as for knn()."""
     L = lib()
     out, args, keep = [], [], []
     for x, s_ in ((feat, sq), (xyz4, None)):
         B, N, Cc = x.shape
-        idx = torch.empty(B, N, k, dtype=torch.int32, device=x.device)
+        idx = _i32(B, N, k, device=x.device, prefill=prefill)
         ties = torch.empty(1 + B * N, dtype=torch.int32, device=x.device)
         args.append(KnnArgs(ptr(x), x.stride(1), ptr(s_), B, N, Cc, k, ptr(idx), ptr(ties), B * N, 0))
         _tie_work(args[-1], N, x.device, keep, slots_for=B if tie_slots else 0)
@@ -451,13 +460,13 @@ def knn_pair(feat, sq, xyz4, k, xt=None, order=None, tie_slots=False):
 
 
 @_guarded
-def knn_pair_deferred(xa, sqa, xb, sqb, k):
+def knn_pair_deferred(xa, sqa, xb, sqb, k, prefill=None):
     """Two kNN launches with tie_defer and ONE vcr_knn_ties_f32 replay for both (the LPDNet pattern) -> (idx_a, idx_b)."""
     L = lib()
     args, keep = [], []
     for x, sq in ((xa, sqa), (xb, sqb)):
         B, N, Cc = x.shape
-        idx = torch.empty(B, N, k, dtype=torch.int32, device=x.device)
+        idx = _i32(B, N, k, device=x.device, prefill=prefill)
         ties = torch.zeros(1 + B * N, dtype=torch.int32, device=x.device)
         a = KnnArgs(ptr(x), x.stride(1), ptr(sq), B, N, Cc, k, ptr(idx), ptr(ties), B * N, 0)
         a.tie_zeroed, a.tie_defer = 1, 1
@@ -660,14 +669,14 @@ def rigid_svd(src, corr, want_h=False):
 @_guarded
 def pairscore(own, strm, nbatch, n_own, n_str, op, score=0, scale=1.0, own_side4=None, str_side4=None,
               shift=0, str_stat2=None, str_stat_stride=None, mass=None, accumulate=False, want_argmax=False,
-              score_out=None, variant=0, split=False):
+              score_out=None, variant=0, split=False, prefill=None):
     """vcr_pairscore_f32: op 0 -> corr4; op 1 -> (stat2 [nbatch*n_own,2], argmax or None); op 2 -> mass.
     score_out (op 1): [nbatch, n_own, ld] buffer that also receives the scores.  split: give the launch scratch to split
     the streamed side over several workgroups when its grid calls for it (op 1 without argmax)."""
     dev = own.device
     corr4 = _f32(nbatch * n_own, 4, device=dev) if op == 0 else None
     stat2 = _f32(nbatch * n_own, 2, device=dev) if op == 1 else None
-    amax = torch.empty(nbatch * n_own, dtype=torch.int32, device=dev) if (op == 1 and want_argmax) else None
+    amax = _i32(nbatch * n_own, device=dev, prefill=prefill) if (op == 1 and want_argmax) else None
     if op == 2 and mass is None:
         mass = _f32(nbatch, n_own, device=dev)
     work = _f32(4 * nbatch * n_own * (8 if op == 0 else 2), device=dev) if split else None
@@ -826,11 +835,15 @@ def segmax(x, M, k, out=None):
 
 
 @_guarded
-def rankselect(values, K, want_order=True, want_mask=False, largest=True):
-    """values [nbatch, n] (any element stride along n, e.g. one column of a [nbatch, n, 2] record)."""
+def rankselect(values, K, want_order=True, want_mask=False, largest=True, prefill=None):
+    """values [nbatch, n] (any element stride along n, e.g. one column of a [nbatch, n, 2] record).  prefill: a value
+    order and mask hold before the launch (mask: its low byte)."""
     nb, n = values.shape
-    order = torch.empty(nb, K, dtype=torch.int32, device=values.device) if want_order else None
-    mask = torch.empty(nb, n, dtype=torch.uint8, device=values.device) if want_mask else None
+    order = _i32(nb, K, device=values.device, prefill=prefill) if want_order else None
+    mask = None
+    if want_mask:
+        mask = torch.empty(nb, n, dtype=torch.uint8, device=values.device) if prefill is None else \
+            torch.full((nb, n), prefill & 0xFF, dtype=torch.uint8, device=values.device)
     stride = values.stride(1) if n > 1 else 1
     if values.stride(0) != n * stride:
         values, stride = values.contiguous(), 1
