@@ -606,6 +606,8 @@ typedef struct {
   int32_t *out_keys, *out_sel_src, *out_sel_tgt, *out_argmax, *out_pairs;
 } vcr_vcrnet_io;
 
+/* Workspace bytes of vcr_vcrnet_forward_f32.  This size query and vcr_vcrnet_iter_workspace_bytes answer for the calling
+ * thread's current device: the layout depends on its CU count. */
 size_t vcr_vcrnet_workspace_bytes(const vcr_vcrnet_weights*, int B, int N);
 /* The same for vcr_vcrnet_iter_f32(iters): with iters > 1 it adds room behind the forward's workspace (2 B N x 2560 floats) for the
  * four buffers whose target-cloud rows the later passes reuse; a workspace of only vcr_vcrnet_workspace_bytes still works -- every

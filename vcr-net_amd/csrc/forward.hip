@@ -10,16 +10,22 @@
 
 namespace {
 
-// Workspace plan (round 5): every buffer of the forward with the launches between which it is LIVE, laid out by a static
-// interval allocator -- buffers whose lifetimes do not overlap share memory.  Rounds 1-4 carved the workspace with a bump
-// allocator (every buffer its own memory: 1.5 GB at BASELINE configs[1], 12 GB at configs[4]); the plan needs what the
-// busiest launch has live (the grouped self-attention: embeddings + enc | dec Q | K | V + both outputs = 9 x [2BN, 512]
-// floats).  Times are positions in the launch sequence of forward_impl (the merged and the unmerged first sublayers have
-// their own numbering up to 15; from the cross-attention's K | V projection on they agree):
-//   0 stem  1 kNN (+ dg1_pq)  2 tie replay  3 EdgeConv / DGCNN chain  4 sn1_pq  5 gathermax  6 conv3
-//   merged:   7 encdec.qkv  8 self-attention  9 wo pair  10 enc.ffn1 + dec.cross.q  11 enc.ffn2
-//   unmerged: 7 enc.qkv  8 enc.self  9 enc.wo  10 enc.ffn1  11 enc.ffn2  12 dec.qkv  13 dec.self  14 dec.self.wo  15 dec.cross.q
-//   16 dec.cross.kv  17 cross-attention  18 dec.cross.wo  19 dec.ffn1  20 dec.ffn2  21 dec.norm / rowside  22 head  23 second head
+// Workspace plan: every buffer of the forward with the launches between which it is LIVE, laid out by a static interval
+// allocator -- buffers whose lifetimes do not overlap share memory.  The workspace is then what the busiest launch has live
+// (the grouped self-attention: embeddings + enc | dec Q | K | V + both outputs = 9 x [2BN, 512] floats), not the sum of all
+// buffers.  A buffer's lifetime is given in these positions of forward_impl's launch sequence:
+enum Launch : int {
+  STEM, KNN, TIE_REPLAY, EDGECONV, SN1_PQ, GATHERMAX, CONV3,   // (KNN: with the split modes' dg1_pq; EDGECONV: DGCNN's whole chain)
+  // merged first sublayers (merged_encdec); the exact-split form launches a pair's two linears one after the other
+  ENCDEC_QKV, ENCDEC_SELF, WO_PAIR, FFN1_CROSS_Q, MERGED_ENC_FFN2,
+  // unmerged first sublayers, numbered from the same position
+  ENC_QKV = ENCDEC_QKV, ENC_SELF, ENC_WO, ENC_FFN1, ENC_FFN2, DEC_QKV, DEC_SELF, DEC_SELF_WO, DEC_CROSS_Q,
+  // both forms from the cross-attention's K | V projection on
+  DEC_CROSS_KV, CROSS_ATT, DEC_CROSS_WO, DEC_FFN1, DEC_FFN2, DEC_NORM, HEAD, HEAD2,   // (DEC_NORM: or rowside)
+  END = HEAD2                                            // the last launch of a forward (vcrnetIter's state lives across forwards)
+};
+static_assert(MERGED_ENC_FFN2 < DEC_CROSS_KV, "the merged first sublayers end in front of the positions both forms share");
+
 struct Plan {
   struct Req { void** slot; size_t bytes; int birth, death; size_t off; };
   static constexpr int MAXR = 96;
@@ -67,7 +73,11 @@ struct Plan {
 struct Ws {
   float *xyz4, *feat64, *sq64, *pq1, *cat, *pq3, *emb;
   int32_t *idx1, *idx3, *ties;                         // ties: 2 x (count + one slot per row) for the kNN tie replay
-  unsigned char* tie_work; size_t tie_work_each;       // 2 x vcr_knn_tie_work_bytes(N): replay scratch of long rows (else NULL)
+  unsigned char* tie_work[2]; size_t tie_work_each;    // kNN tie replay scratch of the feature-space | the Cartesian search (else NULL)
+  float* feat64t;                                      // feat64 in the operand layout of the 16-query kNN waves: emb's first M x 64 floats
+  // the ordered kNN search's arrays (vcr_knn_order_args), in emb behind feat64t
+  float *feat_p, *xyz4_p, *cen64, *cen4, *sq_p, *c64_sq, *c64_rad, *c64_max, *c4_rad, *c4_max;
+  int32_t *perm, *ord_ok;
   float *qkv, *att, *attx, *e1, *e2, *hid, *d1, *d2, *d3, *qc, *kvc, *embf, *side4, *csplit, *asplit;   // att: self-attention output(s), attx: cross
   float* corr_ba;                                      // cycle: the second head's correspondences [B, N, 4]
   long asplit_floats;
@@ -99,15 +109,24 @@ inline size_t tgt_cache_floats(int B, int N, int E) { return (size_t)2 * B * N *
 inline int overlap_k1(int N, double o2) { return (int)((double)N * 0.84 * o2); }
 inline int overlap_k2(int N, double o2) { return (int)((double)overlap_k1(N, o2) * 0.52 * o2); }
 
-Ws carve(void* base, int B, int N, int k, int E, int F, int heads, int partial, double o2, int emb_kind, int xscore_limit_mb,
-         int merged, int flat) {
+// enc.qkv + dec.qkv as one GEMM, the two self-attentions as one grouped launch: needs the stacked folded weight (fp32 mode)
+constexpr int KNN_ORDERED_MIN_N = 2048;                 // clouds from this size on take the ordered kNN search (see the LPDNet stage)
+inline int merged_encdec(const vcr_vcrnet_weights* W) {
+  return W->has_pointer == 1 && (W->linear_mode == 0 || W->split.encdec_qkv) && W->fold_encdec_qkv.w && W->fold_encdec_qkv.colsum &&
+         W->fold_encdec_qkv.bias;
+}
+
+// Every workspace address of a forward.  cus: the CU count of the device the attention launches plan their key split for.
+// pass: forward_impl's (a vcrnetIter pass with target reuse finds emb, d1, qc and kvc behind the plan).
+Ws carve(void* base, const vcr_vcrnet_weights* W, int B, int N, int cus, int pass = 0) {
+  const int k = W->k, E = W->E, F = W->F, heads = W->heads;
+  const bool merged = merged_encdec(W) != 0;
   Plan pl;
-  pl.flat = flat != 0;
+  pl.flat = W->workspace_flat != 0;
   const size_t M = (size_t)2 * B * N;
-  constexpr int END = 23;                                // (the last launch of a forward; vcrnetIter's state lives across forwards)
   Ws w{};
-  pl.want(w.xyz4, M * 4, 0, END);   pl.want(w.feat64, M * 64, 0, 3);   pl.want(w.sq64, M, 0, 2);   // (PointNet: conv3 reads feat64 at 3)
-  pl.want(w.idx1, M * k, 1, 3);     pl.want(w.idx3, M * k, 1, 5);      pl.want(w.ties, 2 * (1 + M), 0, 2);   // a slot for every row
+  pl.want(w.xyz4, M * 4, STEM, END);   pl.want(w.feat64, M * 64, STEM, EDGECONV);   pl.want(w.sq64, M, STEM, TIE_REPLAY);   // (PointNet: conv3 reads feat64 at EDGECONV)
+  pl.want(w.idx1, M * k, KNN, EDGECONV);   pl.want(w.idx3, M * k, KNN, GATHERMAX);   pl.want(w.ties, 2 * (1 + M), STEM, TIE_REPLAY);   // a slot for every row
   // kNN tie replay scratch per search: k > 20 -- slots for the in-launch replay (the lists leave no room for a row image in
   // LDS), while that stays below 1 GiB (live during the kNN launch only: it lies under the Transformer's buffers) --, else what
   // the replay launch needs for rows beyond 10 091 points
@@ -116,22 +135,23 @@ Ws carve(void* base, int B, int N, int k, int E, int F, int heads, int partial, 
     w.tie_work_each = (k > 20 && slots <= ((size_t)1 << 30)) ? slots : vcr_knn_tie_work_bytes(N);
     w.tie_work_each = (w.tie_work_each + 255) & ~(size_t)255;
   }
-  pl.want(w.tie_work, w.tie_work_each ? 2 * w.tie_work_each : 0, 1, 2);
-  pl.want(w.pq1, M * 256, 0, 4);    pl.want(w.cat, M * 512, 3, 6);     pl.want(w.pq3, M * 512, 4, 5);   // (PointNet: conv4 reads pq1 at 4)
-  pl.want(w.emb, M * E, 0, 21);                          // (0 .. 2: the transposed feat64 rows of the 16-query kNN waves; 6 ..: the embeddings)
+  pl.want(w.tie_work[0], w.tie_work_each ? 2 * w.tie_work_each : 0, KNN, TIE_REPLAY);
+  pl.want(w.pq1, M * 256, STEM, SN1_PQ);   pl.want(w.cat, M * 512, EDGECONV, CONV3);   pl.want(w.pq3, M * 512, SN1_PQ, GATHERMAX);   // (PointNet: conv4 reads pq1 at SN1_PQ)
+  pl.want(w.emb, M * E, STEM, DEC_NORM);                 // (in front of CONV3: feat64t and the ordered search's arrays; CONV3 ..: the embeddings)
   // merged: the encoder's and the decoder's Q|K|V side by side ([M, 6E]) and their attention outputs one after the other
-  pl.want(w.qkv, M * 3 * E * (merged ? 2 : 1), 7, merged ? 8 : 13);
-  pl.want(w.att, M * E * (merged ? 2 : 1), 8, merged ? 9 : 14);
-  pl.want(w.e1, M * E, 9, 11);      pl.want(w.e2, M * E, 11, 16);
-  pl.want(w.hid, M * F, 10, 20);                         // (FFN hidden rows of both layers; 17: the dense K | V copy of the exact-split cross-attention)
-  pl.want(w.d1, M * E, merged ? 9 : 14, 18);
-  pl.want(w.qc, M * E, merged ? 10 : 15, 17);            pl.want(w.kvc, M * 2 * E, 16, 17);
-  pl.want(w.attx, M * E, 17, 18);
-  pl.want(w.d2, M * E, 18, END);                         // (23: the VcpAtt projections of the second head)
-  pl.want(w.d3, M * E, 20, END);                         // (22: the VcpAtt projections of the head)
-  pl.want(w.embf, M * E, 21, END);  pl.want(w.side4, M * 4, 21, END);
-  pl.want(w.csplit, VCR_PAIRSCORE_MAX_SPLIT * (M / 2) * 8, 22, END);   // vcr_softcorr_args.split_work of the soft heads
-  pl.want(w.corr_ba, (size_t)B * N * 4, 23, END);
+  pl.want(w.qkv, M * 3 * E * (merged ? 2 : 1), merged ? ENCDEC_QKV : ENC_QKV, merged ? ENCDEC_SELF : DEC_SELF);
+  pl.want(w.att, M * E * (merged ? 2 : 1), merged ? ENCDEC_SELF : ENC_SELF, merged ? WO_PAIR : DEC_SELF_WO);
+  pl.want(w.e1, M * E, merged ? WO_PAIR : ENC_WO, merged ? MERGED_ENC_FFN2 : ENC_FFN2);
+  pl.want(w.e2, M * E, merged ? MERGED_ENC_FFN2 : ENC_FFN2, DEC_CROSS_KV);
+  pl.want(w.hid, M * F, merged ? FFN1_CROSS_Q : ENC_FFN1, DEC_FFN2);   // (FFN hidden rows of both layers; CROSS_ATT: the dense K | V copy of the exact-split cross-attention)
+  pl.want(w.d1, M * E, merged ? WO_PAIR : DEC_SELF_WO, DEC_CROSS_WO);
+  pl.want(w.qc, M * E, merged ? FFN1_CROSS_Q : DEC_CROSS_Q, CROSS_ATT);   pl.want(w.kvc, M * 2 * E, DEC_CROSS_KV, CROSS_ATT);
+  pl.want(w.attx, M * E, CROSS_ATT, DEC_CROSS_WO);
+  pl.want(w.d2, M * E, DEC_CROSS_WO, END);               // (HEAD2: the VcpAtt projections of the second head)
+  pl.want(w.d3, M * E, DEC_FFN2, END);                   // (HEAD: the VcpAtt projections of the head)
+  pl.want(w.embf, M * E, DEC_NORM, END);  pl.want(w.side4, M * 4, DEC_NORM, END);
+  pl.want(w.csplit, VCR_PAIRSCORE_MAX_SPLIT * (M / 2) * 8, HEAD, END);   // vcr_softcorr_args.split_work of the soft heads
+  pl.want(w.corr_ba, (size_t)B * N * 4, HEAD2, END);
   {
     // planes of a key-split attention-output launch (vcr_sdpa_args.split_work; the grouped self-attention has 2 M rows):
     // the library only splits while the planes stay below 64 MB, i.e. at small batches -- no more than that is set aside
@@ -141,57 +161,74 @@ Ws carve(void* base, int B, int N, int k, int E, int F, int heads, int partial, 
     // ... and only for grids of at most half a round: vcr_sdpa_f32 splits the keys when blocks x split <= slots (the same
     // constants and CU count as its launcher; 512 slots on MI355X); the smallest attention-output launch of the forward is the
     // cross-attention (ceil(N / 128) x 2B x heads blocks)
-    if ((long)((N + VCR_SDPA_QROWS - 1) / VCR_SDPA_QROWS) * 2 * B * heads * 2 > (long)vcr_cu_count() * VCR_SDPA_WG_PER_CU) w.asplit_floats = 0;
-    pl.want(w.asplit, (size_t)w.asplit_floats, 8, 17);
+    if ((long)((N + VCR_SDPA_QROWS - 1) / VCR_SDPA_QROWS) * 2 * B * heads * 2 > (long)cus * VCR_SDPA_WG_PER_CU) w.asplit_floats = 0;
+    pl.want(w.asplit, (size_t)w.asplit_floats, merged ? ENCDEC_SELF : ENC_SELF, CROSS_ATT);
   }
   const size_t sn = M * (E / 64) * 2;
-  pl.want(w.st_emb, sn, 6, 12);
-  pl.want(w.st_e1, sn, 9, 10);      pl.want(w.st_e2, sn, 11, 16);
-  pl.want(w.st_d1, sn, merged ? 9 : 14, merged ? 10 : 15);             pl.want(w.st_d2, sn, 18, 19);
-  const size_t K1 = (size_t)overlap_k1(N, o2), K2 = (size_t)overlap_k2(N, o2), B1 = (size_t)B;
-  if (partial) {
-    pl.want(w.rowstat, M * heads * 2, 17, 17); pl.want(w.keymass, M, 17, 17); pl.want(w.keep, M, 17, 17);
-    pl.want(w.xsplit, VCR_SDPA_MAX_SPLIT * M * heads * 2, 17, 17);
+  pl.want(w.st_emb, sn, CONV3, DEC_QKV);                 // (the merged form's last reader is ENCDEC_QKV)
+  pl.want(w.st_e1, sn, merged ? WO_PAIR : ENC_WO, merged ? FFN1_CROSS_Q : ENC_FFN1);
+  pl.want(w.st_e2, sn, merged ? MERGED_ENC_FFN2 : ENC_FFN2, DEC_CROSS_KV);
+  pl.want(w.st_d1, sn, merged ? WO_PAIR : DEC_SELF_WO, merged ? FFN1_CROSS_Q : DEC_CROSS_Q);
+  pl.want(w.st_d2, sn, DEC_CROSS_WO, DEC_FFN1);
+  const size_t K1 = (size_t)overlap_k1(N, W->overlap2), K2 = (size_t)overlap_k2(N, W->overlap2), B1 = (size_t)B;
+  if (W->partial) {
+    pl.want(w.rowstat, M * heads * 2, CROSS_ATT, CROSS_ATT); pl.want(w.keymass, M, CROSS_ATT, CROSS_ATT); pl.want(w.keep, M, CROSS_ATT, CROSS_ATT);
+    pl.want(w.xsplit, VCR_SDPA_MAX_SPLIT * M * heads * 2, CROSS_ATT, CROSS_ATT);
     const size_t xs = M * heads * ((N + 31) & ~31);       // keep the cross-attention scores if they fit 4 GB
-    const size_t xlimit = xscore_limit_mb > 0 ? (size_t)xscore_limit_mb << 20 : xscore_limit_mb < 0 ? 0 : (size_t)4 << 30;
-    pl.want(w.xscore, xs * 4 <= xlimit ? xs : 0, 17, 17);
-    pl.want(w.xorder, M, 17, 17);
-    pl.want(w.rstat, B1 * N * 2, 22, END); pl.want(w.cstat, B1 * N * 2, 22, END);
-    pl.want(w.rsplit, VCR_PAIRSCORE_MAX_SPLIT * B1 * N * 2, 22, END);
+    const int xmb = W->xscore_limit_mb;
+    const size_t xlimit = xmb > 0 ? (size_t)xmb << 20 : xmb < 0 ? 0 : (size_t)4 << 30;
+    pl.want(w.xscore, xs * 4 <= xlimit ? xs : 0, CROSS_ATT, CROSS_ATT);
+    pl.want(w.xorder, M, CROSS_ATT, CROSS_ATT);
+    pl.want(w.rstat, B1 * N * 2, HEAD, END); pl.want(w.cstat, B1 * N * 2, HEAD, END);
+    pl.want(w.rsplit, VCR_PAIRSCORE_MAX_SPLIT * B1 * N * 2, HEAD, END);
     // source-side block first, target-side block right behind it ([2B, ...] like the embeddings): one rank-select and
     // one gather launch then serve both clouds
-    pl.want(w.rowsum, 2 * B1 * N, 22, END);
-    pl.want(w.score, B1 * N * ((N + 31) & ~31), 22, END);
-    pl.want(w.sel_s, 2 * B1 * K1, 22, END);
-    pl.want(w.amax, B1 * K1, 22, END);     pl.want(w.pick, B1 * (K2 ? K2 : 1), 22, END);
-    pl.want(w.so_e, 2 * B1 * K1 * E, 22, END);
-    pl.want(w.so_s, 2 * B1 * K1 * 4, 22, END);
-    pl.want(w.peak, B1 * K1 * 2, 22, END);
+    pl.want(w.rowsum, 2 * B1 * N, HEAD, END);
+    pl.want(w.score, B1 * N * ((N + 31) & ~31), HEAD, END);
+    pl.want(w.sel_s, 2 * B1 * K1, HEAD, END);
+    pl.want(w.amax, B1 * K1, HEAD, END);     pl.want(w.pick, B1 * (K2 ? K2 : 1), HEAD, END);
+    pl.want(w.so_e, 2 * B1 * K1 * E, HEAD, END);
+    pl.want(w.so_s, 2 * B1 * K1 * 4, HEAD, END);
+    pl.want(w.peak, B1 * K1 * 2, HEAD, END);
   }
-  if (emb_kind == 1 && k != 20 && k != 40) {              // (k = 20 / 40 run the chain in one kernel: no per-edge tensor at all)
+  if (W->emb_kind == 1 && k != 20 && k != 40) {           // (k = 20 / 40 run the chain in one kernel: no per-edge tensor at all)
     const size_t Mk = M * k;
-    pl.want(w.eh1, Mk * 64, 3, 5); pl.want(w.eh2, Mk * 64, 3, 5);
-    pl.want(w.eh3, Mk * 128, 3, 5);                        // (conv4's [M*k, 256] output is only ever max-reduced: never stored)
+    pl.want(w.eh1, Mk * 64, EDGECONV, GATHERMAX); pl.want(w.eh2, Mk * 64, EDGECONV, GATHERMAX);
+    pl.want(w.eh3, Mk * 128, EDGECONV, GATHERMAX);        // (conv4's [M*k, 256] output is only ever max-reduced: never stored)
   }
-  pl.want(w.cur_cf, (size_t)B * 3 * N, 0, END);
-  pl.want(w.Ri, (size_t)B * 9, 0, END); pl.want(w.ti, (size_t)B * 3, 0, END);
-  pl.want(w.Rb, (size_t)B * 9, 0, END); pl.want(w.tb, (size_t)B * 3, 0, END);
+  pl.want(w.cur_cf, (size_t)B * 3 * N, STEM, END);
+  pl.want(w.Ri, (size_t)B * 9, STEM, END); pl.want(w.ti, (size_t)B * 3, STEM, END);
+  pl.want(w.Rb, (size_t)B * 9, STEM, END); pl.want(w.tb, (size_t)B * 3, STEM, END);
   w.bytes = pl.solve(reinterpret_cast<unsigned char*>(base)) + 256;
-  if (pl.overflow) w.bytes = ~(size_t)0;                 // (never with the ~60 buffers above: forward_impl then returns VCR_EWORKSPACE)
-  if (partial) {
+  bool bad = pl.overflow;                                // (never with the ~60 buffers above)
+  w.tie_work[1] = w.tie_work[0] ? w.tie_work[0] + w.tie_work_each : nullptr;
+  if (W->partial) {
     w.colsum = w.rowsum + B1 * N;
     w.sel_t = w.sel_s + B1 * K1;
     w.to_e = w.so_e + B1 * K1 * E;
     w.to_s = w.so_s + B1 * K1 * 4;
   }
+  if (pass != 0) {                                       // (the planned copies of these four stay unused in such a loop)
+    float* c = reinterpret_cast<float*>(static_cast<unsigned char*>(base) + w.bytes);
+    w.emb = c;   c += M * E;
+    w.d1 = c;    c += M * E;
+    w.qc = c;    c += M * E;
+    w.kvc = c;
+  }
+  // w.emb is free until conv3 writes the embeddings: feat64t first, the ordered search's arrays behind it
+  w.feat64t = E >= 64 ? w.emb : nullptr;
+  {
+    const size_t T = (size_t)2 * B * ((N + 15) / 16);    // tiles of 16 points
+    float* p = w.emb + M * 64;
+    auto take = [&p](size_t n) { float* q = p; p += n; return q; };
+    w.feat_p = take(M * 64);  w.xyz4_p = take(M * 4);  w.cen64 = take(T * 64);  w.cen4 = take(T * 4);  w.sq_p = take(M);
+    w.perm = reinterpret_cast<int32_t*>(take(M));
+    w.c64_sq = take(T);  w.c64_rad = take(T);  w.c64_max = take(T);  w.c4_rad = take(T);  w.c4_max = take(T);
+    w.ord_ok = reinterpret_cast<int32_t*>(take(2 * B));
+    if (pass != 0 && p > w.emb + B1 * N * E) bad = true;   // they stay clear of the target rows a later pass keeps in emb
+  }
+  if (bad) w.bytes = ~(size_t)0;                         // (forward_impl then returns VCR_EWORKSPACE)
   return w;
-}
-
-// enc.qkv + dec.qkv as one GEMM, the two self-attentions as one grouped launch: needs the stacked folded weight (fp32 mode)
-constexpr int KNN_ORDERED_MIN_N = 2048;                 // clouds from this size on take the ordered kNN search (see the LPDNet stage)
-inline int merged_encdec(const vcr_vcrnet_weights* W) {
-  return W->has_pointer == 1 && (W->linear_mode == 0 || W->split.encdec_qkv) && W->fold_encdec_qkv.w && W->fold_encdec_qkv.colsum &&
-         W->fold_encdec_qkv.bias;
 }
 
 __global__ __launch_bounds__(256) void zero_i32_kernel(int32_t* p, long n) {
@@ -208,6 +245,13 @@ struct Runner {
   // things: such a launch pins the shape the full-row launch it stands for would take (shape_rows = that row count; 0 = off).
   int shape_rows = 0;
   int plan_nbatch = 0;                                   // likewise for the attention launches' key split (vcr_sdpa_args.plan_nbatch)
+  bool sdpa_split = false;                               // linear_mode 2
+  float* pv_split = nullptr; long pv_split_floats = 0;   // vcr_sdpa_args.split_work of the attention-output launches
+  int linear_variant = 0;                                // MFMA shape / k-slab forced by vcr_vcrnet_weights.linear_mfma / linear_bk
+  int sdpa_variant = 0;                                  // vcr_vcrnet_weights.sdpa_variant
+  vcr_knn_args deferred[2];                              // kNN launches whose tie replay is still owed (knn_ties)
+  int n_deferred = 0;
+
   void pin_shape(vcr_linear_args& a, vcr_linear_args* b = nullptr, int full_rows = 0) {   // full_rows: of the launch this one stands for
     const int fm = full_rows ? full_rows : shape_rows;    // (default: the point rows; DGCNN's per-edge linears pass rows x k)
     if (!shape_rows || a.M >= fm || (a.variant & (16 | 1024))) return;
@@ -218,34 +262,26 @@ struct Runner {
     a.variant |= sa ? 16 : 1024;
     if (b) b->variant |= sb ? 16 : 1024;
   }
-  void mark(const char* name) {
-    if (!tr) return;
-    if (tr->count < VCR_TRACE_MAX) tr->names[tr->count] = name;
-    if (tr->events && tr->count < tr->capacity) (void)hipEventRecord((hipEvent_t)tr->events[tr->count], stream);
-    ++tr->count;
+  bool ok(int r) { if (rc == 0 && r != 0) rc = r; return rc == 0; }
+  // Every launch: none once a launch has failed, else its trace mark (the name -- a string literal: the trace keeps the
+  // pointer -- and an event right before the launch), the launch and its return code.
+  template <class F> bool run(const char* name, F&& launch) {
+    if (rc) return false;
+    if (tr) {
+      if (tr->count < VCR_TRACE_MAX) tr->names[tr->count] = name;
+      if (tr->events && tr->count < tr->capacity) (void)hipEventRecord((hipEvent_t)tr->events[tr->count], stream);
+      ++tr->count;
+    }
+    return ok(launch());
   }
-  void finish() {
+  void finish() {                                        // the closing event after the last launch
     if (tr && tr->events && tr->count < tr->capacity) (void)hipEventRecord((hipEvent_t)tr->events[tr->count], stream);
   }
-  bool ok(int r) { if (rc == 0 && r != 0) rc = r; return rc == 0; }
 
   // ln_stats + ln_colsum: LayerNorm folded into this linear (w, b are the folded weight / bias; the row statistics
   // come from the producer's epilogue);
   // stats_out: this launch's epilogue writes the per-64-column (sum, second moment about the segment mean) partials of its
   // output rows for a later LayerNorm (common.h: ln_row_moments).
-  bool linear(const char* nm, const float* x, int ldx, const float* w, const void* wsplit, const float* b, float* y,
-              int ldy, int M, int N, int K, int relu, const float* res = nullptr, int ldr = 0,
-              const float* ln_stats = nullptr, const float* ln_colsum = nullptr, float* stats_out = nullptr) {
-    if (rc) return false;
-    mark(nm);
-    vcr_linear_args a{x, ldx, w, b, res, ldr, y, ldy, M, N, K, relu};
-    if (ln_stats) { a.ln_stats_in = ln_stats; a.ln_nseg = K / 64; a.ln_colsum = ln_colsum; a.ln_eps = 1e-6f; }
-    a.stats_out = stats_out;
-    a.variant = linear_variant;
-    if (!wsplit) pin_shape(a);                           // (the exact-split kernel has one configuration)
-    return ok(wsplit ? vcr_linear_bf16x3_f32(&a, wsplit, stream) : vcr_linear_f32(&a, stream));
-  }
-  // the argument block of linear() without launching it, and two such blocks as one launch (vcr_linear_pair_f32)
   vcr_linear_args linear_args(const float* x, int ldx, const float* w, const float* b, float* y, int ldy, int M, int N, int K,
                               int relu, const float* res = nullptr, int ldr = 0, const float* ln_stats = nullptr,
                               const float* ln_colsum = nullptr, float* stats_out = nullptr) {
@@ -255,112 +291,106 @@ struct Runner {
     a.variant = linear_variant;
     return a;
   }
+  // one linear launch: its trace name, its arguments and its exact-split weight (NULL: fp32)
+  struct Lin { const char* name; vcr_linear_args a; const void* split; };
+  bool linear(const Lin& l) {
+    return run(l.name, [&] {
+      vcr_linear_args a = l.a;
+      if (!l.split) pin_shape(a);                        // (the exact-split kernel has one configuration)
+      return l.split ? vcr_linear_bf16x3_f32(&a, l.split, stream) : vcr_linear_f32(&a, stream);
+    });
+  }
+  bool linear(const char* nm, const float* x, int ldx, const float* w, const void* wsplit, const float* b, float* y,
+              int ldy, int M, int N, int K, int relu, const float* res = nullptr, int ldr = 0,
+              const float* ln_stats = nullptr, const float* ln_colsum = nullptr, float* stats_out = nullptr) {
+    return linear({nm, linear_args(x, ldx, w, b, y, ldy, M, N, K, relu, res, ldr, ln_stats, ln_colsum, stats_out), wsplit});
+  }
+  // two independent fp32 linears as one launch (vcr_linear_pair_f32)
   bool linear2(const char* nm, vcr_linear_args a, vcr_linear_args b) {
-    if (rc) return false;
-    mark(nm);
-    pin_shape(a, &b);
-    return ok(vcr_linear_pair_f32(&a, &b, stream));
+    return run(nm, [&] {
+      pin_shape(a, &b);
+      return vcr_linear_pair_f32(&a, &b, stream);
+    });
   }
   bool norm(const char* nm, const float* x, const vcr_norm_w& n, float* y, int M, int E,
             const float* res = nullptr, const float* xyz4 = nullptr, float* side4 = nullptr) {
-    if (rc) return false;
-    mark(nm);
-    vcr_layernorm_args a{x, E, n.ln_a, n.ln_b, 1e-6f, res, E, y, E, M, E, xyz4, side4};
-    return ok(vcr_layernorm_f32(&a, stream));
+    return run(nm, [&] {
+      vcr_layernorm_args a{x, E, n.ln_a, n.ln_b, 1e-6f, res, E, y, E, M, E, xyz4, side4};
+      return vcr_layernorm_f32(&a, stream);
+    });
   }
   bool sdpa(const char* nm, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* out,
             int ldo, int nb, int heads, int nq, int nk, int shift, const uint8_t* keep = nullptr,
             float* rowstat = nullptr, float* score_out = nullptr, int ld_score = 0, int ngroups = 1, long in_group_stride = 0,
             long out_group_stride = 0, float* split_work = nullptr, long split_floats = 0) {
-    if (rc) return false;
-    mark(nm);
-    vcr_sdpa_args a{q, ldq, k, ldk, v, ldv, out, ldo, nb, heads, nq, nk, 1.0f / sqrtf(128.f), shift, keep, rowstat,
-                    score_out, ld_score};
-    // key split: statistics passes bring their own scratch; attention-output launches share the driver's planes (only
-    // taken by vcr_sdpa_f32 for grids of less than one round, i.e. small batches)
-    a.split_work = split_work ? split_work : out ? pv_split : nullptr;
-    a.split_work_floats = split_work ? split_floats : out ? pv_split_floats : 0;
-    if (ngroups > 1) {
-      a.ngroups = ngroups; a.q_group_stride = a.k_group_stride = a.v_group_stride = in_group_stride;
-      a.out_group_stride = out_group_stride;
-    }
-    a.variant = sdpa_variant;
-    if (plan_nbatch > nb) a.plan_nbatch = plan_nbatch;    // (a source-only launch of a later vcrnetIter pass: split as the full one)
-    // linear_mode 2: the attention-output launches on the bf16 matrix pipe as exact splits; statistics passes stay fp32
-    return ok((sdpa_split && out && !rowstat && !score_out) ? vcr_sdpa_bf16x3_f32(&a, stream) : vcr_sdpa_f32(&a, stream));
+    return run(nm, [&] {
+      vcr_sdpa_args a{q, ldq, k, ldk, v, ldv, out, ldo, nb, heads, nq, nk, 1.0f / sqrtf(128.f), shift, keep, rowstat,
+                      score_out, ld_score};
+      // key split: statistics passes bring their own scratch; attention-output launches share the driver's planes (only
+      // taken by vcr_sdpa_f32 for grids of less than one round, i.e. small batches)
+      a.split_work = split_work ? split_work : out ? pv_split : nullptr;
+      a.split_work_floats = split_work ? split_floats : out ? pv_split_floats : 0;
+      if (ngroups > 1) {
+        a.ngroups = ngroups; a.q_group_stride = a.k_group_stride = a.v_group_stride = in_group_stride;
+        a.out_group_stride = out_group_stride;
+      }
+      a.variant = sdpa_variant;
+      if (plan_nbatch > nb) a.plan_nbatch = plan_nbatch;  // (a source-only launch of a later vcrnetIter pass: split as the full one)
+      // linear_mode 2: the attention-output launches on the bf16 matrix pipe as exact splits; statistics passes stay fp32
+      return (sdpa_split && out && !rowstat && !score_out) ? vcr_sdpa_bf16x3_f32(&a, stream) : vcr_sdpa_f32(&a, stream);
+    });
   }
   bool pairscore(const char* nm, const vcr_pairscore_args& a) {
-    if (rc) return false;
-    mark(nm);
-    return ok(vcr_pairscore_f32(&a, stream));
+    return run(nm, [&] { return vcr_pairscore_f32(&a, stream); });
   }
   bool rank(const char* nm, const float* values, int stride, int nb, int n, int K, int32_t* order, uint8_t* mask,
             int largest) {
-    if (rc) return false;
-    mark(nm);
-    vcr_rankselect_args a{values, nb, n, K, order, mask, largest, stride};
-    return ok(vcr_rankselect_f32(&a, stream));
+    return run(nm, [&] {
+      vcr_rankselect_args a{values, nb, n, K, order, mask, largest, stride};
+      return vcr_rankselect_f32(&a, stream);
+    });
   }
   bool gather(const char* nm, const float* in, int ld, int n_in, const int32_t* idx, int nb, int n_out, int C,
               float* out, const int32_t* via = nullptr, int n_via = 0) {
-    if (rc) return false;
-    mark(nm);
-    vcr_gather_args a{in, ld, n_in, idx, nb, n_out, C, out, C, via, n_via};
-    return ok(vcr_gather_rows_f32(&a, stream));
+    return run(nm, [&] {
+      vcr_gather_args a{in, ld, n_in, idx, nb, n_out, C, out, C, via, n_via};
+      return vcr_gather_rows_f32(&a, stream);
+    });
+  }
+
+  // kNN launches: the tie counters were zeroed together at the start of the forward; a launch that does not replay its
+  // tied rows itself (long rows) is listed in `deferred` and replayed by knn_ties() before the first consumer of the indices
+  void knn(const char* nm, vcr_knn_args a) {
+    a.tie_zeroed = 1;
+    run(nm, [&] { return vcr_knn_f32(&a, stream); });
+  }
+  // LPDNet's two independent searches as one launch (vcr_knn_pair_f32), their tie replays deferred to knn_ties()
+  void knn_pair(const char* nm, vcr_knn_args a64, vcr_knn_args a3) {
+    run(nm, [&] {
+      a64.tie_zeroed = a3.tie_zeroed = 1;
+      a64.tie_defer = a3.tie_defer = 1;
+      n_deferred = 0;                                    // (a launch that replays its ties itself owes nothing)
+      int inl64 = 0, inl3 = 0;
+      (void)vcr_knn_forms_(&a64, &a3, nullptr, &inl64, &inl3);
+      if (!inl64) deferred[n_deferred++] = a64;
+      if (!inl3) deferred[n_deferred++] = a3;
+      return vcr_knn_pair_f32(&a64, &a3, stream);
+    });
+  }
+  // one replay launch for every kNN deferred so far: to be called before the first consumer of any of their indices
+  void knn_ties() {
+    if (n_deferred) run("knn:ties", [&] { return vcr_knn_ties_f32(&deferred[0], n_deferred == 2 ? &deferred[1] : nullptr, stream); });
+    n_deferred = 0;
+  }
+  // device-to-device copy of a forced / reported selection (tiny; stays on the stream)
+  void copy_idx(const char* nm, int32_t* dst, const int32_t* src, size_t n) {
+    run(nm, [&] { return vcr_copy_d2d(dst, src, n * sizeof(int32_t), stream); });
   }
 
   // Decoder cross-attention.  Partial mode (transformer.py:35-53): soft-max once, total probability mass every
   // KEY receives over heads and queries, keep the int(nk*overlap2) heaviest keys, soft-max again over those.
   // The first soft-max is never written: a statistics pass leaves (max, sum) per query row, the mass pass
   // streams the queries past each key block (owner = keys of batch b, streamed = queries of batch (b+B) % 2B).
-  // kNN launches: the tie counters were zeroed together at the start of the forward; a launch that does not replay its
-  // tied rows itself (long rows) is listed in `deferred` and replayed by knn_ties() before the first consumer of the indices
-  const vcr_vcrnet_io* io_ = nullptr;
-  bool sdpa_split = false;                               // linear_mode 2
-  float* pv_split = nullptr; long pv_split_floats = 0;   // vcr_sdpa_args.split_work of the attention-output launches
-  int linear_variant = 0;                                // MFMA shape / k-slab forced by vcr_vcrnet_weights.linear_mfma / linear_bk
-  int sdpa_variant = 0;                                  // vcr_vcrnet_weights.sdpa_variant
-  vcr_knn_args deferred[2];                              // kNN launches whose tie replay is still owed (knn_ties)
-  int n_deferred = 0;
-  void knn(const char* nm, vcr_knn_args a, int which, bool defer = false) {
-    if (rc) return;
-    mark(nm);
-    a.tie_zeroed = 1;
-    int inl = 0;                                         // (inline: the launch replays its own ties; bad args: the launch says so)
-    (void)vcr_knn_forms_(&a, nullptr, nullptr, &inl, nullptr);
-    if (defer && n_deferred < 2 && !inl) {
-      a.tie_defer = 1;
-      deferred[n_deferred++] = a;
-    }
-    ok(vcr_knn_f32(&a, stream));
-  }
-  // LPDNet's two independent searches as one launch (vcr_knn_pair_f32), their tie replays deferred to knn_ties()
-  void knn_pair(const char* nm, vcr_knn_args a64, vcr_knn_args a3) {
-    if (rc) return;
-    mark(nm);
-    a64.tie_zeroed = a3.tie_zeroed = 1;
-    a64.tie_defer = a3.tie_defer = 1;
-    n_deferred = 0;                                      // (a launch that replays its ties itself owes nothing)
-    int inl64 = 0, inl3 = 0;
-    (void)vcr_knn_forms_(&a64, &a3, nullptr, &inl64, &inl3);
-    if (!inl64) deferred[n_deferred++] = a64;
-    if (!inl3) deferred[n_deferred++] = a3;
-    ok(vcr_knn_pair_f32(&a64, &a3, stream));
-  }
-  // one replay launch for every kNN deferred so far: to be called before the first consumer of any of their indices
-  void knn_ties() {
-    if (rc || n_deferred == 0) return;
-    mark("knn:ties");
-    ok(vcr_knn_ties_f32(&deferred[0], n_deferred == 2 ? &deferred[1] : nullptr, stream));
-    n_deferred = 0;
-  }
-  // device-to-device copy of a forced / reported selection (tiny; stays on the stream)
-  void copy_idx(const char* nm, int32_t* dst, const int32_t* src, size_t n) {
-    if (rc) return;
-    mark(nm);
-    ok(vcr_copy_d2d(dst, src, n * sizeof(int32_t), stream));
-  }
-
   void cross_attention(const vcr_vcrnet_weights* W, const vcr_vcrnet_io* io, const Ws& w, int B, int N) {
     const int E = W->E, H = W->heads, nb = 2 * B, dk = E / H;
     const uint8_t* keep = nullptr;
@@ -375,11 +405,10 @@ struct Runner {
         const int ldS = (N + 31) & ~31;
         sdpa("sdpa:dec.cross.stats", w.qc, E, w.kvc, 2 * E, nullptr, 0, nullptr, 0, nb, H, N, N, B, nullptr, w.rowstat,
              w.xscore, ldS, 1, 0, 0, w.xsplit, (long)VCR_SDPA_MAX_SPLIT * nb * H * N * 2);
-        if (rc == 0) {
-          mark("scoremass:dec.cross.keymass");
+        run("scoremass:dec.cross.keymass", [&] {
           vcr_keymass_args a{w.xscore, ldS, nb, H, N, N, w.rowstat, B, w.keymass};
-          ok(vcr_keymass_f32(&a, stream));
-        }
+          return vcr_keymass_f32(&a, stream);
+        });
       } else {                                           // score matrix too large to keep: recompute it per head
         sdpa("sdpa:dec.cross.stats", w.qc, E, w.kvc, 2 * E, nullptr, 0, nullptr, 0, nb, H, N, N, B, nullptr, w.rowstat, nullptr, 0,
              1, 0, 0, w.xsplit, (long)VCR_SDPA_MAX_SPLIT * nb * H * N * 2);
@@ -400,11 +429,11 @@ struct Runner {
       if (!io->force_keys) rank("select:dec.cross.keys", w.keymass, 1, nb, N, nkeep, w.xorder, w.keep, 1);
       if (io->out_keys) copy_idx("select:dec.cross.keys.out", io->out_keys, w.xorder, (size_t)nb * nkeep);
       if (!sdpa_split && nkeep <= 16384) {               // (vcr_sdpa_f32 holds the index list in LDS: <= 16 384 kept keys;
-        if (rc) return;                                  //  longer lists take the dense copy / the masked form below)
-        mark("sdpa:dec.cross");
-        vcr_sdpa_args a{w.qc, E, w.kvc, 2 * E, w.kvc + E, 2 * E, w.attx, E, nb, H, N, nkeep, 1.0f / sqrtf(128.f), B};
-        a.key_index = w.xorder; a.nk_src = N;
-        ok(vcr_sdpa_f32(&a, stream));
+        run("sdpa:dec.cross", [&] {                      //  longer lists take the dense copy / the masked form below)
+          vcr_sdpa_args a{w.qc, E, w.kvc, 2 * E, w.kvc + E, 2 * E, w.attx, E, nb, H, N, nkeep, 1.0f / sqrtf(128.f), B};
+          a.key_index = w.xorder; a.nk_src = N;
+          return vcr_sdpa_f32(&a, stream);
+        });
         return;
       }
       if (W->F >= 2 * E) {
@@ -441,11 +470,10 @@ struct Runner {
     const bool forced_sets = io->force_sel_src && io->force_sel_tgt;
     if (!forced_sets) {
       stats("pairscore:head.scores", se, te, ss, ts, N, N, w.rstat, nullptr, w.score, ldS);
-      if (rc == 0) {
-        mark("scoremass:head");
-        vcr_scoremass_args a{w.score, ldS, B, N, N, w.rstat, w.cstat, w.colsum, w.rowsum};           // :222, :244
-        ok(vcr_scoremass_f32(&a, stream));
-      }
+      run("scoremass:head", [&] {
+        vcr_scoremass_args a{w.score, ldS, B, N, N, w.rstat, w.cstat, w.colsum, w.rowsum};             // :222, :244
+        return vcr_scoremass_f32(&a, stream);
+      });
     }
     if (forced_sets) {
       copy_idx("select:head.tgt.forced", w.sel_t, io->force_sel_tgt, (size_t)B * K1);
@@ -468,10 +496,10 @@ struct Runner {
     if (io->out_pairs) copy_idx("select:head.pairs.out", io->out_pairs, w.pick, (size_t)B * K2);
     gather("select:gather.srcK", w.so_s, 4, K1, w.pick, B, K2, 4, io->src4);                         // :328-330
     gather("select:gather.corrK", w.to_s, 4, K1, w.pick, B, K2, 4, io->corr4, w.amax, K1);           // :325 (weights == 1)
-    if (rc) return;
-    mark("rigid_svd:ab");
-    vcr_rigid_svd_args a{io->src4, 4, io->corr4, 4, B, K2, io->R_ab, io->t_ab, io->R_ba, io->t_ba, nullptr};
-    ok(vcr_rigid_svd_f32(&a, stream));
+    run("rigid_svd:ab", [&] {
+      vcr_rigid_svd_args a{io->src4, 4, io->corr4, 4, B, K2, io->R_ab, io->t_ab, io->R_ba, io->t_ba, nullptr};
+      return vcr_rigid_svd_f32(&a, stream);
+    });
   }
 };
 
@@ -511,22 +539,14 @@ int forward_impl(const vcr_vcrnet_weights* W, const vcr_vcrnet_io* io, void* wor
   if (!W->partial && (io->force_keys || io->force_sel_src || io->force_sel_tgt || io->force_argmax || io->force_pairs))
     return VCR_EINVAL;                                   // there is nothing discrete to force in whole mode
   if ((io->force_sel_src != nullptr) != (io->force_sel_tgt != nullptr)) return VCR_EINVAL;
-  Ws w = carve(workspace, B, N, k, E, F, W->heads, W->partial, W->overlap2, W->emb_kind, W->xscore_limit_mb, merged_encdec(W), W->workspace_flat);
+  Ws w = carve(workspace, W, B, N, vcr_cu_count(), pass);
   if (ws_bytes < w.bytes) return VCR_EWORKSPACE;
+  if (pass != 0 && ws_bytes < w.bytes + tgt_cache_floats(B, N, E) * sizeof(float)) return VCR_EINVAL;
   const int M1 = B * N, M2 = 2 * M1;
-  if (pass != 0) {
-    if (ws_bytes < w.bytes + tgt_cache_floats(B, N, E) * sizeof(float)) return VCR_EINVAL;
-    float* c = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + w.bytes);
-    w.emb = c;       c += (size_t)M2 * E;                // (the planned copies of these four stay unused in such a loop)
-    w.d1 = c;        c += (size_t)M2 * E;
-    w.qc = c;        c += (size_t)M2 * E;
-    w.kvc = c;
-  }
   const bool half = pass == 2;                           // launches in front of the cross-attention: source rows only
   const int Bq = half ? B : 2 * B, Mq = half ? M1 : M2;
 #define NM(site) (half ? site "@src" : site)
   Runner R{(hipStream_t)stream, tr};
-  R.io_ = io;
   R.shape_rows = half ? M2 : 0;
   R.plan_nbatch = half ? 2 * B : 0;
   // both tie counters (and the first block).  A kernel, not hipMemsetAsync: the forward then records into a HIP graph of
@@ -546,15 +566,16 @@ int forward_impl(const vcr_vcrnet_weights* W, const vcr_vcrnet_io* io, void* wor
     // split (per-point P/Q + gather), conv2..conv4 as N*k-row GEMMs, max over the k edges after each, conv5 on the
     // 512-wide concatenation.  BatchNorm (eval mode) is folded into the weights by the host.  (linear_mode 1 / 2: the
     // embedding's own GEMMs stay fp32 MFMA -- the chain kernel has no split variant -- the Transformer takes the mode.)
-    for (int c = 0; c < (half ? 1 : 2) && R.rc == 0; ++c) {   // rows (x, y, z, |p|^2) and conv1's per-point (P | Q), one pass
-      R.mark(c ? "pointwise:tgt" : "pointwise:src");
-      R.ok(vcr_rows4_pq_f32(c ? io->tgt_cf : io->src_cf, w.xyz4 + (size_t)c * M1 * 4, B, N, W->dgcnn.c1_wpq, 32,
-                            W->dgcnn.c1_bpq, 128, w.pq1 + (size_t)c * M1 * 128, 128, R.stream));
+    for (int c = 0; c < (half ? 1 : 2); ++c) {           // rows (x, y, z, |p|^2) and conv1's per-point (P | Q), one pass
+      R.run(c ? "pointwise:tgt" : "pointwise:src", [&] {
+        return vcr_rows4_pq_f32(c ? io->tgt_cf : io->src_cf, w.xyz4 + (size_t)c * M1 * 4, B, N, W->dgcnn.c1_wpq, 32,
+                                W->dgcnn.c1_bpq, 128, w.pq1 + (size_t)c * M1 * 128, 128, R.stream);
+      });
     }
     {
       vcr_knn_args a3{(uint32_t)sizeof(vcr_knn_args), w.xyz4, 4, nullptr, Bq, N, 4, k, w.idx3, w.ties + 1 + M2, M2};
-      a3.tie_work = w.tie_work; a3.tie_work_bytes = w.tie_work_each;
-      R.knn(NM("knn:xyz"), a3, 1);
+      a3.tie_work = w.tie_work[0]; a3.tie_work_bytes = w.tie_work_each;
+      R.knn(NM("knn:xyz"), a3);
     }
     const int Mk = Mq * k;
     // Every x.max(dim=-1) of vcrnet_model.py:109-118 rides on the kernel that produces the per-edge rows: the edge-row
@@ -562,28 +583,26 @@ int forward_impl(const vcr_vcrnet_weights* W, const vcr_vcrnet_io* io, void* wor
     // epilogues (integer atomic max on post-ReLU values), and conv4's 256-wide per-edge activations are never written.
     auto conv_max = [&](const char* nm, const float* x, int K, const float* wt, const float* bias, float* y, int Nout,
                         int col) {
-      if (R.rc) return;
-      R.mark(nm);
-      vcr_linear_args a{x, K, wt, bias, nullptr, 0, y, Nout, Mk, Nout, K, 1};
-      a.segmax_out = w.cat + col; a.ld_segmax = 512; a.seg_k = k;
-      a.variant = R.linear_variant;                      // (vcr_vcrnet_weights.linear_mfma / linear_bk / linear_bm reach every fp32 linear)
-      R.pin_shape(a, nullptr, M2 * k);                   // (a source-only pass: the MFMA shape of the launch over both clouds' edges)
-      R.ok(vcr_linear_f32(&a, R.stream));
+      R.run(nm, [&] {
+        vcr_linear_args a{x, K, wt, bias, nullptr, 0, y, Nout, Mk, Nout, K, 1};
+        a.segmax_out = w.cat + col; a.ld_segmax = 512; a.seg_k = k;
+        a.variant = R.linear_variant;                    // (vcr_vcrnet_weights.linear_mfma / linear_bk / linear_bm reach every fp32 linear)
+        R.pin_shape(a, nullptr, M2 * k);                 // (a source-only pass: the MFMA shape of the launch over both clouds' edges)
+        return vcr_linear_f32(&a, R.stream);
+      });
     };
     if (k == 20 || k == 40) {
       // the path's k: the whole chain in one kernel, the per-edge activations stay in LDS (edgechain.hip)
-      if (R.rc == 0) {
-        R.mark(NM("edgeconv:dg_chain"));
+      R.run(NM("edgeconv:dg_chain"), [&] {
         vcr_edgechain_args a{w.pq1, 128, w.idx3, k, Mq, N, W->dgcnn.c2_w, W->dgcnn.c2_b, W->dgcnn.c3_w, W->dgcnn.c3_b,
                              W->dgcnn.c4_w, W->dgcnn.c4_b, w.cat, 512};
-        R.ok(vcr_edgechain_f32(&a, R.stream));
-      }
+        return vcr_edgechain_f32(&a, R.stream);
+      });
     } else {
-      if (R.rc == 0) {
-        R.mark(NM("gathermax:dg_c1"));
+      R.run(NM("gathermax:dg_c1"), [&] {
         vcr_edgerows_args a{w.pq1, 128, 64, w.idx3, k, Mq, N, w.eh1, 64, w.cat, 512, 512};
-        R.ok(vcr_edgerows_f32(&a, R.stream));
-      }
+        return vcr_edgerows_f32(&a, R.stream);
+      });
       conv_max(NM("linear:dg_c2"), w.eh1, 64, W->dgcnn.c2_w, W->dgcnn.c2_b, w.eh2, 64, 64);
       conv_max(NM("linear:dg_c3"), w.eh2, 64, W->dgcnn.c3_w, W->dgcnn.c3_b, w.eh3, 128, 128);
       conv_max(NM("linear:dg_c4"), w.eh3, 128, W->dgcnn.c4_w, W->dgcnn.c4_b, nullptr, 256, 256);
@@ -593,12 +612,11 @@ int forward_impl(const vcr_vcrnet_weights* W, const vcr_vcrnet_io* io, void* wor
   } else if (W->emb_kind == 2) {
     // ---- emb_nn = PointNet on both clouds (vcrnet_model.py:81-87): five pointwise convs + BatchNorm (eval mode, folded
     // into weight and bias by the host) + ReLU, no graph.  conv1 / conv2 have the shape of LPDNet's stem: same kernel.
-    if (R.rc == 0) {
-      R.mark(NM("pointwise:src+tgt"));
+    R.run(NM("pointwise:src+tgt"), [&] {
       vcr_pointwise_args a{io->src_cf, B, N, W->c1_w, W->c1_b, W->c2_w, W->c2_b, w.xyz4, w.feat64, w.sq64, half ? nullptr : io->tgt_cf,
                            half ? 0 : B};
-      R.ok(vcr_pointwise_f32(&a, R.stream));
-    }
+      return vcr_pointwise_f32(&a, R.stream);
+    });
     R.linear(NM("linear:pn_c3"), w.feat64, 64, W->pointnet.c3_w, nullptr, W->pointnet.c3_b, w.pq1, 64, Mq, 64, 64, 1);
     R.linear(NM("linear:pn_c4"), w.pq1, 64, W->pointnet.c4_w, nullptr, W->pointnet.c4_b, w.cat, 128, Mq, 128, 64, 1);
     R.linear(NM("linear:pn_c5"), w.cat, 128, W->pointnet.c5_w, nullptr, W->pointnet.c5_b, w.emb, E, Mq, E, 128, 1, nullptr, 0, nullptr,
@@ -611,68 +629,54 @@ int forward_impl(const vcr_vcrnet_weights* W, const vcr_vcrnet_io* io, void* wor
   // the exact split, and the accuracy ledger's `trained` k = 40 fixture left its bound (R error vs the float64 twin 4.3e-6 ->
   // 5.9e-6 against 1.5 x the reference's + 3e-6 = 4.9e-6).  Reverted.)
   const bool pq_fused = W->linear_mode == 0;
-  if (R.rc == 0) {                                       // both clouds in one launch: rows 0..M1-1 = src, then tgt
-    R.mark(pq_fused ? NM("pointwise:src+tgt+dg1_pq") : NM("pointwise:src+tgt"));
+  R.run(pq_fused ? NM("pointwise:src+tgt+dg1_pq") : NM("pointwise:src+tgt"), [&] {   // both clouds in one launch: rows 0..M1-1 = src, then tgt
     vcr_pointwise_args a{io->src_cf, B, N, W->c1_w, W->c1_b, W->c2_w, W->c2_b, w.xyz4, w.feat64, w.sq64, half ? nullptr : io->tgt_cf,
                          half ? 0 : B};
     if (pq_fused) { a.pq_w = W->dg1_wpq; a.pq_b = W->dg1_bpq; a.pq = w.pq1; a.ldpq = 256; }
-    a.feat64t = W->E >= 64 ? w.emb : nullptr;                                   // operand layout of the 16-query kNN waves (w.emb is free until conv3)
-    R.ok(vcr_pointwise_f32(&a, R.stream));
-  }
+    a.feat64t = w.feat64t;
+    return vcr_pointwise_f32(&a, R.stream);
+  });
   // The feature-space and the Cartesian kNN (lpdnet_model.py:113,129) are independent: one launch for both, and one
   // tie replay for both right before the first consumer of the indices.
   const int32_t* rank_perm = nullptr;                    // the clouds' Morton ranking, when the kNN took the ordered search
   {
     vcr_knn_args a64{(uint32_t)sizeof(vcr_knn_args), w.feat64, 64, w.sq64, Bq, N, 64, k, w.idx1, w.ties, M2, W->knn_waves};
     vcr_knn_args a3{(uint32_t)sizeof(vcr_knn_args), w.xyz4, 4, nullptr, Bq, N, 4, k, w.idx3, w.ties + 1 + M2, M2};
-    a64.tie_work = w.tie_work; a3.tie_work = w.tie_work ? w.tie_work + w.tie_work_each : nullptr;
+    a64.tie_work = w.tie_work[0]; a3.tie_work = w.tie_work[1];
     a64.tie_work_bytes = a3.tie_work_bytes = w.tie_work_each;
-    a64.xt = W->E >= 64 ? w.emb : nullptr;
+    a64.xt = w.feat64t;
     // The ORDERED search (vcr_knn_args.perm) for the larger clouds: ranking the points along a Morton curve lets a 16-query
     // wave skip the tiles whose balls cannot hold a neighbour -- measured (profiles/rounds4-5/r5o_knn_ordered.txt) 416 -> 295 + 45 us
     // (ranking) at 32 x 2048, 2970 -> 1850 + 93 at 64 x 4096, k = 40; at 1024 points the plain scan is faster (120 vs 143 + 30).
-    // Its arrays live in the unused part of w.emb (free until conv3; feat64t is its first M2 x 64 floats).
     int pair_ordered = 0;                                // (the library's choice: only the pair's fused 16-query form reads the ranking)
     if (R.rc == 0 && W->E >= 256 && N >= KNN_ORDERED_MIN_N && N <= 8192 && (k == 20 || k == 40) && W->knn_waves == 0 &&
         vcr_knn_forms_(&a64, &a3, &pair_ordered, nullptr, nullptr) == VCR_OK && pair_ordered) {
-      const size_t m = (size_t)M2, mt = (size_t)2 * B * ((N + 15) / 16);
-      float* base = w.emb + m * 64;
-      float* feat_p = base;                 base += m * 64;
-      float* xyz4_p = base;                 base += m * 4;
-      float* cen64 = base;                  base += mt * 64;
-      float* cen4 = base;                   base += mt * 4;
-      float* sq_p = base;                   base += m;
-      int32_t* perm = reinterpret_cast<int32_t*>(base);   base += m;
-      float* c64_sq = base;  base += mt;  float* c64_rad = base;  base += mt;  float* c64_max = base;  base += mt;
-      float* c4_rad = base;  base += mt;  float* c4_max = base;  base += mt;
-      int32_t* ord_ok = reinterpret_cast<int32_t*>(base);                  // the ranking's per-cloud verdict on the feature tiles
-      R.mark(NM("knn:rank"));
-      vcr_knn_order_args o{w.xyz4, w.emb, 64, w.sq64, Bq, N, perm, xyz4_p, cen4, c4_rad, c4_max, feat_p, sq_p, cen64, c64_sq,
-                           c64_rad, c64_max, ord_ok, nullptr, 0.f};
-      R.ok(vcr_knn_order_f32(&o, R.stream));
-      a64.perm = a3.perm = perm;
-      a64.ord_ok = ord_ok;
-      rank_perm = perm;                                  // (lives in w.emb until conv3 writes the embeddings: gathermax runs before)
-      a64.xp = feat_p; a64.sqp = sq_p; a64.cen = cen64; a64.cen_sq = c64_sq; a64.cen_rad = c64_rad; a64.cen_sqmax = c64_max;
-      a3.xp = xyz4_p; a3.cen = cen4; a3.cen_rad = c4_rad; a3.cen_sqmax = c4_max;
+      R.run(NM("knn:rank"), [&] {
+        vcr_knn_order_args o{w.xyz4, w.feat64t, 64, w.sq64, Bq, N, w.perm, w.xyz4_p, w.cen4, w.c4_rad, w.c4_max, w.feat_p, w.sq_p,
+                             w.cen64, w.c64_sq, w.c64_rad, w.c64_max, w.ord_ok, nullptr, 0.f};
+        return vcr_knn_order_f32(&o, R.stream);
+      });
+      a64.perm = a3.perm = w.perm;
+      a64.ord_ok = w.ord_ok;
+      rank_perm = w.perm;                                // (lives in w.emb until conv3 writes the embeddings: gathermax runs before)
+      a64.xp = w.feat_p; a64.sqp = w.sq_p; a64.cen = w.cen64; a64.cen_sq = w.c64_sq; a64.cen_rad = w.c64_rad; a64.cen_sqmax = w.c64_max;
+      a3.xp = w.xyz4_p; a3.cen = w.cen4; a3.cen_rad = w.c4_rad; a3.cen_sqmax = w.c4_max;
     }
     R.knn_pair(NM("knn:feat64+xyz"), a64, a3);
   }
   if (!pq_fused) R.linear(NM("linear:dg1_pq"), w.feat64, 64, W->dg1_wpq, SP(dg1_pq), W->dg1_bpq, w.pq1, 256, Mq, 256, 64, 0);
   R.knn_ties();                                          // both tie replays in one launch (one latency instead of two)
-  if (R.rc == 0) {
-    R.mark(NM("edgeconv:dg1_dg2"));
+  R.run(NM("edgeconv:dg1_dg2"), [&] {
     vcr_edgeconv_args a{w.pq1, 256, w.idx1, k, Mq, N, W->dg2_w, W->dg2_b, w.cat, 512, w.cat + 128, 512};
     // (linear_mode 1 / 2: convDG2 as exact bf16 splits at the path's k; other k keep the fp32 kernel)
-    R.ok(W->linear_mode != 0 && (k == 20 || k == 40) ? vcr_edgeconv_bf16x3_f32(&a, R.stream) : vcr_edgeconv_f32(&a, R.stream));
-  }
+    return W->linear_mode != 0 && (k == 20 || k == 40) ? vcr_edgeconv_bf16x3_f32(&a, R.stream) : vcr_edgeconv_f32(&a, R.stream);
+  });
   R.linear(NM("linear:sn1_pq"), w.cat + 128, 512, W->sn1_wpq, SP(sn1_pq), W->sn1_bpq, w.pq3, 512, Mq, 512, 128, 0);
-  if (R.rc == 0) {
-    R.mark(NM("gathermax:sn1"));
+  R.run(NM("gathermax:sn1"), [&] {
     vcr_gathermax_args a{w.pq3, 512, 256, w.idx3, k, Mq, N, w.cat + 256, 512};
     a.order = rank_perm;                                 // (clouds that were ranked for the kNN: the L2 form walks them in rank order)
-    R.ok(vcr_gathermax_f32(&a, R.stream));
-  }
+    return vcr_gathermax_f32(&a, R.stream);
+  });
   R.linear(NM("linear:conv3"), w.cat, 512, W->c3_w, SP(c3), W->c3_b, w.emb, E, Mq, E, 512, 1, nullptr, 0, nullptr, nullptr,
            W->has_pointer == 1 ? w.st_emb : nullptr);
 
@@ -688,7 +692,21 @@ int forward_impl(const vcr_vcrnet_weights* W, const vcr_vcrnet_io* io, void* wor
     // 2 x 67 MB round trips are gone.
     const int H = W->heads;
     const bool merged = merged_encdec(W) != 0;
-    const float* att_dec = w.att;                        // the decoder's self-attention output
+    const float* att_dec = merged ? w.att + (size_t)M2 * E : w.att;   // the decoder's self-attention output
+    // the five linears between the self-attentions and the cross-attention's K | V projection; the forms below only order
+    // them, and pair them or not
+    using Lin = Runner::Lin;
+    const Lin enc_wo{NM("linear:enc.wo"), R.linear_args(w.att, E, W->enc_self.wo, W->enc_self.bo, w.e1, E, Mq, E, E, 0, w.emb, E,
+                                                         nullptr, nullptr, w.st_e1), SP(enc_wo)};
+    const Lin dec_self_wo{NM("linear:dec.self.wo"), R.linear_args(att_dec, E, W->dec_self.wo, W->dec_self.bo, w.d1, E, Mq, E, E, 0,
+                                                                  w.emb, E, nullptr, nullptr, w.st_d1), SP(dec_self_wo)};
+    const Lin enc_ffn1{NM("linear:enc.ffn1"), R.linear_args(w.e1, E, W->fold_enc_ffn1.w, W->fold_enc_ffn1.bias, w.hid, F, Mq, F, E, 1,
+                                                            nullptr, 0, w.st_e1, W->fold_enc_ffn1.colsum), SP(enc_ffn1)};
+    const Lin dec_cross_q{NM("linear:dec.cross.q"), R.linear_args(w.d1, E, W->fold_dec_cross_q.w, W->fold_dec_cross_q.bias, w.qc, E, Mq,
+                                                                  E, E, 0, nullptr, 0, w.st_d1, W->fold_dec_cross_q.colsum),
+                          SP(dec_cross_q)};
+    const Lin enc_ffn2{NM("linear:enc.ffn2"), R.linear_args(w.hid, F, W->enc_ffn.w2, W->enc_ffn.b2, w.e2, E, Mq, E, F, 0, w.e1, E,
+                                                            nullptr, nullptr, w.st_e2), SP(enc_ffn2)};
     if (merged) {
       // both first sublayers read the embedding rows with the same row statistics: one [M, 6E] projection, and the two
       // independent self-attentions as one grouped launch (group 0 = encoder, 1 = decoder)
@@ -696,53 +714,27 @@ int forward_impl(const vcr_vcrnet_weights* W, const vcr_vcrnet_io* io, void* wor
                nullptr, 0, w.st_emb, W->fold_encdec_qkv.colsum);
       R.sdpa(NM("sdpa:encdec.self"), w.qkv, 6 * E, w.qkv + E, 6 * E, w.qkv + 2 * E, 6 * E, w.att, E, Bq, H, N, N, 0, nullptr, nullptr,
              nullptr, 0, 2, 3 * E, (long)M2 * E);
-      att_dec = w.att + (size_t)M2 * E;
+      if (W->linear_mode != 0) {
+        // the split-arithmetic linears have no paired launcher: the same sequence, one launch each
+        R.linear(enc_wo); R.linear(dec_self_wo); R.linear(enc_ffn1); R.linear(dec_cross_q); R.linear(enc_ffn2);
+      } else {
+        // independent launches of one kernel configuration run as pairs: the two output projections (inputs = the two
+        // attention outputs, residual = the embedding), then the encoder's FFN-in beside the decoder's cross-attention query
+        R.linear2(NM("linear:enc.wo+dec.self.wo"), enc_wo.a, dec_self_wo.a);
+        R.linear2(NM("linear:enc.ffn1+dec.cross.q"), enc_ffn1.a, dec_cross_q.a);
+        R.linear(enc_ffn2);
+      }
     } else {
-    R.linear(NM("linear:enc.qkv"), w.emb, E, W->fold_enc_qkv.w, SP(enc_qkv), W->fold_enc_qkv.bias, w.qkv, 3 * E, Mq, 3 * E, E, 0,
-             nullptr, 0, w.st_emb, W->fold_enc_qkv.colsum);
-    R.sdpa(NM("sdpa:enc.self"), w.qkv, 3 * E, w.qkv + E, 3 * E, w.qkv + 2 * E, 3 * E, w.att, E, Bq, H, N, N, 0);
-    }
-    if (merged && W->linear_mode != 0) {
-      // the split-arithmetic linears have no paired launcher: the same sequence, one launch each
-      R.linear(NM("linear:enc.wo"), w.att, E, W->enc_self.wo, SP(enc_wo), W->enc_self.bo, w.e1, E, Mq, E, E, 0, w.emb, E,
-               nullptr, nullptr, w.st_e1);
-      R.linear(NM("linear:dec.self.wo"), att_dec, E, W->dec_self.wo, SP(dec_self_wo), W->dec_self.bo, w.d1, E, Mq, E, E, 0, w.emb, E,
-               nullptr, nullptr, w.st_d1);
-      R.linear(NM("linear:enc.ffn1"), w.e1, E, W->fold_enc_ffn1.w, SP(enc_ffn1), W->fold_enc_ffn1.bias, w.hid, F, Mq, F, E, 1, nullptr, 0,
-               w.st_e1, W->fold_enc_ffn1.colsum);
-      R.linear(NM("linear:dec.cross.q"), w.d1, E, W->fold_dec_cross_q.w, SP(dec_cross_q), W->fold_dec_cross_q.bias, w.qc, E, Mq, E, E, 0, nullptr, 0,
-               w.st_d1, W->fold_dec_cross_q.colsum);
-      R.linear(NM("linear:enc.ffn2"), w.hid, F, W->enc_ffn.w2, SP(enc_ffn2), W->enc_ffn.b2, w.e2, E, Mq, E, F, 0, w.e1, E,
-               nullptr, nullptr, w.st_e2);
-    } else if (merged) {
-      // independent launches of one kernel configuration run as pairs: the two output projections (inputs = the two
-      // attention outputs, residual = the embedding), then the encoder's FFN-in beside the decoder's cross-attention query
-      R.linear2(NM("linear:enc.wo+dec.self.wo"),
-                R.linear_args(w.att, E, W->enc_self.wo, W->enc_self.bo, w.e1, E, Mq, E, E, 0, w.emb, E, nullptr, nullptr, w.st_e1),
-                R.linear_args(att_dec, E, W->dec_self.wo, W->dec_self.bo, w.d1, E, Mq, E, E, 0, w.emb, E, nullptr, nullptr, w.st_d1));
-      R.linear2(NM("linear:enc.ffn1+dec.cross.q"),
-                R.linear_args(w.e1, E, W->fold_enc_ffn1.w, W->fold_enc_ffn1.bias, w.hid, F, Mq, F, E, 1, nullptr, 0, w.st_e1,
-                              W->fold_enc_ffn1.colsum),
-                R.linear_args(w.d1, E, W->fold_dec_cross_q.w, W->fold_dec_cross_q.bias, w.qc, E, Mq, E, E, 0, nullptr, 0, w.st_d1,
-                              W->fold_dec_cross_q.colsum));
-      R.linear(NM("linear:enc.ffn2"), w.hid, F, W->enc_ffn.w2, nullptr, W->enc_ffn.b2, w.e2, E, Mq, E, F, 0, w.e1, E,
-               nullptr, nullptr, w.st_e2);
-    } else {
-    R.linear(NM("linear:enc.wo"), w.att, E, W->enc_self.wo, SP(enc_wo), W->enc_self.bo, w.e1, E, Mq, E, E, 0, w.emb, E,
-             nullptr, nullptr, w.st_e1);
-    R.linear(NM("linear:enc.ffn1"), w.e1, E, W->fold_enc_ffn1.w, SP(enc_ffn1), W->fold_enc_ffn1.bias, w.hid, F, Mq, F, E, 1, nullptr, 0,
-             w.st_e1, W->fold_enc_ffn1.colsum);
-    R.linear(NM("linear:enc.ffn2"), w.hid, F, W->enc_ffn.w2, SP(enc_ffn2), W->enc_ffn.b2, w.e2, E, Mq, E, F, 0, w.e1, E,
-             nullptr, nullptr, w.st_e2);
-    // decoder; batch b attends to the encoder memory (= enc.norm(e2), applied inside the K/V projection) of
-    // batch (b + B) mod 2B
-    R.linear(NM("linear:dec.qkv"), w.emb, E, W->fold_dec_qkv.w, SP(dec_qkv), W->fold_dec_qkv.bias, w.qkv, 3 * E, Mq, 3 * E, E, 0,
-             nullptr, 0, w.st_emb, W->fold_dec_qkv.colsum);
-    R.sdpa(NM("sdpa:dec.self"), w.qkv, 3 * E, w.qkv + E, 3 * E, w.qkv + 2 * E, 3 * E, w.att, E, Bq, H, N, N, 0);
-    R.linear(NM("linear:dec.self.wo"), att_dec, E, W->dec_self.wo, SP(dec_self_wo), W->dec_self.bo, w.d1, E, Mq, E, E, 0, w.emb, E,
-             nullptr, nullptr, w.st_d1);
-    R.linear(NM("linear:dec.cross.q"), w.d1, E, W->fold_dec_cross_q.w, SP(dec_cross_q), W->fold_dec_cross_q.bias, w.qc, E, Mq, E, E, 0, nullptr, 0,
-             w.st_d1, W->fold_dec_cross_q.colsum);
+      R.linear(NM("linear:enc.qkv"), w.emb, E, W->fold_enc_qkv.w, SP(enc_qkv), W->fold_enc_qkv.bias, w.qkv, 3 * E, Mq, 3 * E, E, 0,
+               nullptr, 0, w.st_emb, W->fold_enc_qkv.colsum);
+      R.sdpa(NM("sdpa:enc.self"), w.qkv, 3 * E, w.qkv + E, 3 * E, w.qkv + 2 * E, 3 * E, w.att, E, Bq, H, N, N, 0);
+      R.linear(enc_wo); R.linear(enc_ffn1); R.linear(enc_ffn2);
+      // decoder; batch b attends to the encoder memory (= enc.norm(e2), applied inside the K/V projection) of
+      // batch (b + B) mod 2B
+      R.linear(NM("linear:dec.qkv"), w.emb, E, W->fold_dec_qkv.w, SP(dec_qkv), W->fold_dec_qkv.bias, w.qkv, 3 * E, Mq, 3 * E, E, 0,
+               nullptr, 0, w.st_emb, W->fold_dec_qkv.colsum);
+      R.sdpa(NM("sdpa:dec.self"), w.qkv, 3 * E, w.qkv + E, 3 * E, w.qkv + 2 * E, 3 * E, w.att, E, Bq, H, N, N, 0);
+      R.linear(dec_self_wo); R.linear(dec_cross_q);
     }
     // batch b attends to the encoder memory (= enc.norm(e2), applied inside the K/V projection) of batch (b + B) mod 2B
     R.linear(NM("linear:dec.cross.kv"), w.e2, E, W->fold_dec_cross_kv.w, SP(dec_cross_kv), W->fold_dec_cross_kv.bias, w.kvc, 2 * E, Mq, 2 * E, E, 0,
@@ -756,10 +748,11 @@ int forward_impl(const vcr_vcrnet_weights* W, const vcr_vcrnet_io* io, void* wor
              w.st_d2, W->fold_dec_ffn1.colsum);
     R.linear("linear:dec.ffn2", w.hid, F, W->dec_ffn.w2, SP(dec_ffn2), W->dec_ffn.b2, w.d3, E, M2, E, F, 0, w.d2, E);
     R.norm("layernorm:dec.norm+res", w.d3, W->dec_norm, w.embf, M2, E, w.emb, w.xyz4, w.side4);
-  } else if (R.rc == 0) {
-    R.mark("layernorm:rowside");
-    vcr_rowside_args a{w.emb, E, M2, E, W->has_pointer == 2 ? 2.f : 1.f, w.embf, E, w.xyz4, w.side4};
-    R.ok(vcr_rowside_f32(&a, R.stream));
+  } else {
+    R.run("layernorm:rowside", [&] {
+      vcr_rowside_args a{w.emb, E, M2, E, W->has_pointer == 2 ? 2.f : 1.f, w.embf, E, w.xyz4, w.side4};
+      return vcr_rowside_f32(&a, R.stream);
+    });
   }
 
   // ---- head + SVD
@@ -772,31 +765,30 @@ int forward_impl(const vcr_vcrnet_weights* W, const vcr_vcrnet_io* io, void* wor
     R.linear("linear:head.att.src", w.embf, E, W->att_w0, nullptr, W->att_b0, w.d3, E, M1, E, E, 0);
     R.linear("linear:head.att.tgt", w.embf + (size_t)M1 * E, E, W->att_w1, nullptr, W->att_b1, w.d3 + (size_t)M1 * E, E,
              M1, E, E, 0);
-    if (R.rc == 0) {
-      R.mark("layernorm:rowside.att");
+    R.run("layernorm:rowside.att", [&] {
       vcr_rowside_args a{w.d3, E, M2, E, 1.f, nullptr, E, w.xyz4, w.side4};
-      R.ok(vcr_rowside_f32(&a, R.stream));
-    }
+      return vcr_rowside_f32(&a, R.stream);
+    });
     head_emb = w.d3;
   }
   auto soft_head = [&](const char* nm, size_t q0, size_t k0, float* corr) {   // rows q0.. are the queries, k0.. the keys
-    if (R.rc) return;
-    R.mark(nm);
-    vcr_softcorr_args a{head_emb + q0 * E, E, head_emb + k0 * E, E, side + q0 * 4, side + k0 * 4,
-                        corr, B, N, N, E, W->head_mode == 1 ? 1 : 0, 1.0f / sqrtf((float)E), w.csplit,
-                        (long)VCR_PAIRSCORE_MAX_SPLIT * B * N * 8};
-    R.ok(vcr_softcorr_f32(&a, R.stream));
+    R.run(nm, [&] {
+      vcr_softcorr_args a{head_emb + q0 * E, E, head_emb + k0 * E, E, side + q0 * 4, side + k0 * 4,
+                          corr, B, N, N, E, W->head_mode == 1 ? 1 : 0, 1.0f / sqrtf((float)E), w.csplit,
+                          (long)VCR_PAIRSCORE_MAX_SPLIT * B * N * 8};
+      return vcr_softcorr_f32(&a, R.stream);
+    });
   };
   if (hard_pairs) {
     R.partial_head(W, io, w, B, N);
   } else {
     soft_head("softcorr:head", 0, (size_t)M1, io->corr4);
-    if (R.rc == 0) {
-      R.mark("rigid_svd:ab");
-      R.ok(vcr_copy_d2d(io->src4, w.xyz4, (size_t)M1 * 4 * sizeof(float), R.stream));
+    R.run("rigid_svd:ab", [&] {
+      const int c = vcr_copy_d2d(io->src4, w.xyz4, (size_t)M1 * 4 * sizeof(float), R.stream);
       vcr_rigid_svd_args a{w.xyz4, 4, io->corr4, 4, B, N, io->R_ab, io->t_ab, io->R_ba, io->t_ba, nullptr};
-      R.ok(vcr_rigid_svd_f32(&a, R.stream));
-    }
+      const int s = vcr_rigid_svd_f32(&a, R.stream);
+      return c ? c : s;
+    });
     if (W->cycle) {
       // cycle consistency (vcrnet_model.py:511-513): a second head + solve with the roles swapped gives (R_ba, t_ba)
       // instead of the inverse of (R_ab, t_ab)
@@ -808,19 +800,17 @@ int forward_impl(const vcr_vcrnet_weights* W, const vcr_vcrnet_io* io, void* wor
         R.linear("linear:head.att.ba.src", w.embf, E, W->att_w1, nullptr, W->att_b1, w.d2, E, M1, E, E, 0);
         R.linear("linear:head.att.ba.tgt", w.embf + (size_t)M1 * E, E, W->att_w0, nullptr, W->att_b0, w.d2 + (size_t)M1 * E,
                  E, M1, E, E, 0);
-        if (R.rc == 0) {
-          R.mark("layernorm:rowside.att.ba");
+        R.run("layernorm:rowside.att.ba", [&] {
           vcr_rowside_args a{w.d2, E, M2, E, 1.f, nullptr, E, w.xyz4, w.side4};
-          R.ok(vcr_rowside_f32(&a, R.stream));
-        }
+          return vcr_rowside_f32(&a, R.stream);
+        });
         head_emb = w.d2;
       }
       soft_head("softcorr:head.ba", (size_t)M1, 0, w.corr_ba);
-      if (R.rc == 0) {
-        R.mark("rigid_svd:ba");
+      R.run("rigid_svd:ba", [&] {
         vcr_rigid_svd_args a{w.xyz4 + (size_t)M1 * 4, 4, w.corr_ba, 4, B, N, io->R_ba, io->t_ba, nullptr, nullptr, nullptr};
-        R.ok(vcr_rigid_svd_f32(&a, R.stream));
-      }
+        return vcr_rigid_svd_f32(&a, R.stream);
+      });
     }
   }
   if (R.rc == 0 && io->emb_out) R.ok(vcr_copy_d2d(io->emb_out, w.embf, (size_t)M2 * E * sizeof(float), R.stream));
@@ -884,7 +874,7 @@ extern "C" size_t vcr_vcrnet_workspace_bytes(const vcr_vcrnet_weights* UW, int B
   vcr_vcrnet_weights Wn;
   const vcr_vcrnet_weights* W = &Wn;
   if (weights_take(UW, &Wn) || B <= 0 || N <= 0) return 0;
-  return carve(nullptr, B, N, W->k, W->E, W->F, W->heads, W->partial, W->overlap2, W->emb_kind, W->xscore_limit_mb, merged_encdec(W), W->workspace_flat).bytes;
+  return carve(nullptr, W, B, N, vcr_cu_count()).bytes;
 }
 
 // vcrnetIter with target reuse: more than one pass, not switched off (vcr_vcrnet_weights.iter_reuse == 1).  Every embedding
@@ -895,7 +885,7 @@ extern "C" size_t vcr_vcrnet_iter_workspace_bytes(const vcr_vcrnet_weights* UW, 
   vcr_vcrnet_weights Wn;
   const vcr_vcrnet_weights* W = &Wn;
   if (weights_take(UW, &Wn) || B <= 0 || N <= 0 || iters < 1) return 0;
-  const size_t base = carve(nullptr, B, N, W->k, W->E, W->F, W->heads, W->partial, W->overlap2, W->emb_kind, W->xscore_limit_mb, merged_encdec(W), W->workspace_flat).bytes;
+  const size_t base = carve(nullptr, W, B, N, vcr_cu_count()).bytes;
   return base + (iter_reuse_applies(W, iters) ? tgt_cache_floats(B, N, W->E) * sizeof(float) : 0);
 }
 
@@ -936,14 +926,15 @@ extern "C" int vcr_vcrnet_iter_f32(const vcr_vcrnet_weights* UW, const vcr_vcrne
     const int rc = forward_impl(W, io, ws, bytes, stream, tr, !W->cycle);
     if (rc || !W->cycle) return rc;
     Runner R{(hipStream_t)stream, tr};
-    R.mark("pose:inverse");
-    hipLaunchKernelGGL(pose_step_kernel, dim3(1, B), dim3(64), 0, (hipStream_t)stream, io->R_ab, io->t_ab, nullptr, nullptr, N,
-                       2, nullptr, nullptr, io->R_ba, io->t_ba);
-    const int lrc = VCR_LAUNCH_RC();
+    R.run("pose:inverse", [&] {
+      hipLaunchKernelGGL(pose_step_kernel, dim3(1, B), dim3(64), 0, R.stream, io->R_ab, io->t_ab, nullptr, nullptr, N, 2, nullptr,
+                         nullptr, io->R_ba, io->t_ba);
+      return VCR_LAUNCH_RC();
+    });
     R.finish();
-    return lrc;
+    return R.rc;
   }
-  const Ws w = carve(ws, B, N, W->k, W->E, W->F, W->heads, W->partial, W->overlap2, W->emb_kind, W->xscore_limit_mb, merged_encdec(W), W->workspace_flat);
+  const Ws w = carve(ws, W, B, N, vcr_cu_count());
   if (bytes < w.bytes) return VCR_EWORKSPACE;
   // target reuse (forward_impl, `pass`): taken when the caller sized the workspace with vcr_vcrnet_iter_workspace_bytes
   const bool reuse = iter_reuse_applies(W, iters) && bytes >= w.bytes + tgt_cache_floats(B, N, W->E) * sizeof(float);
@@ -966,12 +957,12 @@ extern "C" int vcr_vcrnet_iter_f32(const vcr_vcrnet_weights* UW, const vcr_vcrne
     if (rc) return rc;
     if (last && it == 0) break;
     Runner R{(hipStream_t)stream, tr};
-    R.mark("pose:step");
-    hipLaunchKernelGGL(pose_step_kernel, dim3((N + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, step.R_ab,
-                       step.t_ab, step.src_cf, last ? nullptr : w.cur_cf, N, it > 0 ? 1 : 0, io->R_ab, io->t_ab,
-                       io->R_ba, io->t_ba);
-    const int lrc = VCR_LAUNCH_RC();
-    if (lrc) return lrc;
+    R.run("pose:step", [&] {
+      hipLaunchKernelGGL(pose_step_kernel, dim3((N + 255) / 256, B), dim3(256), 0, R.stream, step.R_ab, step.t_ab, step.src_cf,
+                         last ? nullptr : w.cur_cf, N, it > 0 ? 1 : 0, io->R_ab, io->t_ab, io->R_ba, io->t_ba);
+      return VCR_LAUNCH_RC();
+    });
+    if (R.rc) return R.rc;
     if (last) R.finish();
   }
   return VCR_OK;
