@@ -287,6 +287,43 @@ def test_linear_launch_choice_against_the_recorded_sweep(lib):
     assert n >= 30 and worst <= 0.06, (n, worst)
 
 
+def test_sdpa_launch_form_of_the_quoted_shapes(lib):
+    """vcr_sdpa_forms_ (host-only, library-internal): what sdpa_plan makes of the attention launches DESIGN and the tests quote,
+    on 256 CUs -- MI355X's count, and the one the library assumes without a GPU."""
+    from vcrnet_amd import native
+    lib.vcr_sdpa_forms_.argtypes = [ctypes.POINTER(native.SdpaArgs), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.vcr_sdpa_forms_.restype = ctypes.c_int
+
+    def form(nb, nq, nk, out=True, groups=1, split_floats=0, key_index=False):
+        a = native.SdpaArgs()
+        a.q, a.k, a.v = 0x1000, 0x2000, 0x3000                # (never dereferenced on the host)
+        a.ldq = a.ldk = a.ldv = a.ldo = 512
+        a.nbatch, a.heads, a.nq, a.nk, a.scale = nb, 4, nq, nk, 128 ** -0.5
+        if out:
+            a.out = 0x4000
+        else:                                                # statistics pass: (max, sum) rows and the kept scores
+            a.rowstat, a.score_out, a.ld_score = 0x5000, 0x6000, (nk + 31) & ~31
+        if groups > 1:
+            a.ngroups, a.q_group_stride = groups, 1536
+            a.k_group_stride = a.v_group_stride = a.out_group_stride = 1536
+        if split_floats:
+            a.split_work, a.split_work_floats = 0x7000, split_floats
+        if key_index:
+            a.key_index, a.nk_src = 0x8000, nk
+        nsplit, persist = ctypes.c_int(-1), ctypes.c_int(-1)
+        rc = lib.vcr_sdpa_forms_(ctypes.byref(a), ctypes.byref(nsplit), ctypes.byref(persist))
+        return rc, nsplit.value, persist.value
+    # configs[2] cross-attention statistics pass, 48 x 4 heads x 768: 1152 workgroups on 512 slots -> four key runs each
+    assert form(48, 768, 768, out=False, split_floats=4 * 48 * 4 * 768 * 2) == (0, 4, 0)
+    # configs[1] grouped self-attention, 2 groups x 32 x 1024: 2048 items, the persistent kernel, no split
+    assert form(32, 1024, 1024, groups=2) == (0, 1, 1)
+    # an attention-output launch of 2 x 1024 (64 workgroups) with planes for every split: split
+    assert form(2, 1024, 1024, split_floats=4 * (2 * 1024 * 512 + 2 * 4 * 1024 * 2)) == (0, 4, 0)
+    # the key-index form holds its list in LDS: 16 384 kept keys at most
+    assert form(2, 1024, 16384, key_index=True) == (0, 1, 0)
+    assert form(2, 1024, 16385, key_index=True)[0] == -1
+
+
 def test_module_contract_on_cpu():
     """Constructor / state-dict contract of the reference module without a GPU."""
     from types import SimpleNamespace

@@ -507,21 +507,19 @@ __global__ __launch_bounds__(64 * KM_WAVES) void keymass4_kernel(vcr_keymass_arg
   }
 }
 
-}  // namespace
+// How one vcr_sdpa_f32 launch runs.  sdpa_plan() decides it from the arguments, and it is the only place that does.
+enum class SdpaMerge { none, rowstat, output };         // after a key split: rowstat_merge_kernel / sdpa_merge_kernel
+struct SdpaPlan {
+  bool persist, mask, pv;    // sdpa_persist_kernel, else sdpa_kernel<mask = key_keep given, pv = out given>
+  int nsplit, nitems;        // key runs per query block (1: none); the persistent kernel's work items
+  dim3 grid, block; int lds;
+  SdpaMerge merge; long rows; dim3 merge_grid;           // the merge and the rows it combines
+};
+constexpr int SDPA_QROWS = 128, SDPA_WG_PER_CU = 2;     // query rows of a workgroup; resident workgroups per CU (__launch_bounds__)
+constexpr size_t SDPA_PLANE_CAP = (size_t)64 << 20;      // bytes of partial outputs a key-split attention-output launch may write
+long sdpa_blocks(int nq, int heads, long nbatch) { return (long)((nq + SDPA_QROWS - 1) / SDPA_QROWS) * heads * nbatch; }
 
-extern "C" int vcr_keymass_f32(const vcr_keymass_args* a, vcr_stream_t stream) {
-  if (!a || !a->score || !a->rowstat || !a->mass) return VCR_EINVAL;
-  if (a->nbatch <= 0 || a->heads <= 0 || a->nq <= 0 || a->nk <= 0 || a->ld < a->nk) return VCR_EINVAL;
-  // 16 B per lane when every row is 16-B aligned and padded to a multiple of 4 keys (vcr_sdpa_f32's score_out is)
-  if ((a->ld & 3) == 0 && (((uintptr_t)a->score) & 15) == 0 && ((a->nk + 3) & ~3) <= a->ld)
-    hipLaunchKernelGGL(keymass4_kernel, dim3((a->nk + 255) / 256, a->nbatch), dim3(64 * KM_WAVES), 0, (hipStream_t)stream, *a);
-  else
-    hipLaunchKernelGGL(keymass_kernel, dim3((a->nk + 63) / 64, a->nbatch), dim3(256), 0, (hipStream_t)stream, *a);
-  return VCR_LAUNCH_RC();
-}
-
-extern "C" int vcr_sdpa_f32(const vcr_sdpa_args* a, vcr_stream_t stream) {
-  vcr_stream_scope bound(stream);
+int sdpa_plan(const vcr_sdpa_args* a, SdpaPlan* p) {
   if (!a || !a->q || !a->k) return VCR_EINVAL;
   const bool pv = a->out != nullptr;
   if (pv && !a->v) return VCR_EINVAL;
@@ -533,17 +531,19 @@ extern "C" int vcr_sdpa_f32(const vcr_sdpa_args* a, vcr_stream_t stream) {
   const int ng = a->ngroups > 1 ? a->ngroups : 1;
   if (ng > 1 && (!pv || a->key_keep || a->rowstat || a->score_out)) return VCR_EINVAL;
   if (a->key_index && (a->nk_src < 1 || a->key_keep || a->score_out || ng > 1 || a->nk > 16384)) return VCR_EINVAL;
+  if (a->plan_nbatch != 0 && a->plan_nbatch < a->nbatch) return VCR_EINVAL;
+  if (a->variant != 0 && a->variant != 1 && a->variant != 2) return VCR_EINVAL;
+  // the fast attention-output form: no mask, index list, statistics or scores
+  const bool fast = pv && !a->key_keep && !a->key_index && !a->rowstat && !a->score_out && a->scale > 0.f;
+  const long blocks = sdpa_blocks(a->nq, a->heads, a->nbatch) * ng, slots = (long)vcr_cu_count() * SDPA_WG_PER_CU;
+  // (the split decisions count the blocks of the launch this one stands for: vcr_sdpa_args.plan_nbatch)
+  const long plan_blocks = a->plan_nbatch ? blocks / a->nbatch * a->plan_nbatch : blocks;
+  const int ntiles = (a->nk + 31) / 32;
+  int nsplit = 1;
   // Statistics passes (no P V, caller scratch given) split the keys over nsplit workgroups per query block when that
   // shortens the launch by a tenth in a simple round model (a partial last round filled to f costs 0.35 + 0.65 f of a round):
   // 1152 workgroups on 512 slots at BASELINE configs[2] = 2.25 rounds -> four times as many of a quarter the length.
-  const long blocks = (long)((a->nq + VCR_SDPA_QROWS - 1) / VCR_SDPA_QROWS) * a->heads * a->nbatch * ng;
-  if (a->plan_nbatch != 0 && a->plan_nbatch < a->nbatch) return VCR_EINVAL;
-  // (the split decisions below count the blocks of the launch this one stands for: vcr_sdpa_args.plan_nbatch)
-  const long plan_blocks = a->plan_nbatch ? blocks / a->nbatch * a->plan_nbatch : blocks;
-  int nsplit = 1;
   if (!pv && a->split_work && a->split_work_floats >= (long)VCR_SDPA_MAX_SPLIT * a->nbatch * a->heads * a->nq * 2) {
-    const long slots = (long)vcr_cu_count() * 2;
-    const int ntiles = (a->nk + 31) / 32;
     auto cost = [&](int sp) {
       const long t = plan_blocks * sp, full = t / slots;
       const double f = (double)(t - full * slots) / slots;
@@ -560,49 +560,79 @@ extern "C" int vcr_sdpa_f32(const vcr_sdpa_args* a, vcr_stream_t stream) {
   // Attention-output launches of LESS than one round of workgroups (small batches: 64 .. 512 on 512 resident) split the
   // keys too: every workgroup writes its unnormalised partial output and (max, sum) to a plane of the scratch, one more
   // kernel merges the planes (partial outputs: nsplit x the output bytes -- only worth it while that is a few MB).
-  if (pv && a->split_work && !a->rowstat && !a->score_out && a->scale > 0.f && !a->key_keep && !a->key_index) {
-    const long slots = (long)vcr_cu_count() * VCR_SDPA_WG_PER_CU;
-    const int ntiles = (a->nk + 31) / 32;
+  if (fast && a->split_work) {
     const size_t plane = (size_t)ng * a->nbatch * a->nq * a->ldo * 4;
     const size_t plan_plane = plane / a->nbatch * (a->plan_nbatch ? a->plan_nbatch : a->nbatch);     // (of the launch this one stands for)
     const size_t plan_ml = (size_t)ng * (a->plan_nbatch ? a->plan_nbatch : a->nbatch) * a->heads * a->nq * 8;
     for (int sp = VCR_SDPA_MAX_SPLIT; sp >= 2; sp >>= 1)
-      if (plan_blocks * sp <= slots && ntiles / sp >= 4 && (sp - 1) * ((ntiles + sp - 1) / sp) < ntiles && plan_plane * sp <= ((size_t)64 << 20) &&
+      if (plan_blocks * sp <= slots && ntiles / sp >= 4 && (sp - 1) * ((ntiles + sp - 1) / sp) < ntiles && plan_plane * sp <= SDPA_PLANE_CAP &&
           (size_t)a->split_work_floats * 4 >= sp * (plan_plane + plan_ml)) {
         nsplit = sp;
         break;
       }
   }
-  dim3 grid((unsigned)(blocks * nsplit));
-  const int lds = 2 * sizeof(Stage) + (a->key_index ? ((a->nk * 4 + 15) & ~15) : 0);
-  hipStream_t s = (hipStream_t)stream;
   // The persistent kernel where it applies (the fast attention-output form with at least two items per workgroup) unless
   // vcr_sdpa_args.variant asks for the tile kernel: same bits; measured inside the forward (profiles/r6c_sdpa_variant_bench.txt,
   // alternated on one box) sdpa 1.570 -> 1.559 ms per step at configs[1], 6.18 -> 6.07 at configs[3]'s share, 4.86 -> 4.80 at
   // configs[2], level at configs[4] (48.1 ms: 128 key tiles per item, the item boundary is 1 % of an item there)
-  if (a->variant != 0 && a->variant != 1 && a->variant != 2) return VCR_EINVAL;
-  if (a->variant != 1 && pv && nsplit == 1 && !a->key_keep && !a->key_index && !a->rowstat && !a->score_out && a->scale > 0.f &&
-      blocks >= 2 * (long)vcr_cu_count() * 2) {
-    const int lds_p = 2 * sizeof(Stage);
-    VCR_DYN_LDS(sdpa_persist_kernel, lds_p);
-    hipLaunchKernelGGL(sdpa_persist_kernel, dim3((unsigned)(vcr_cu_count() * 2)), dim3(256), lds_p, s, *a, (int)blocks);
-    return VCR_LAUNCH_RC();
-  }
-#define VCR_SDPA_LAUNCH(M, P)                                                                                         \
-  do {                                                                                                                 \
-    VCR_DYN_LDS((sdpa_kernel<M, P>), lds);                                                                             \
-    hipLaunchKernelGGL((sdpa_kernel<M, P>), grid, dim3(256), lds, s, *a, nsplit);                                     \
-  } while (0)
-  if (a->key_keep) { if (pv) VCR_SDPA_LAUNCH(true, true); else VCR_SDPA_LAUNCH(true, false); }
-  else             { if (pv) VCR_SDPA_LAUNCH(false, true); else VCR_SDPA_LAUNCH(false, false); }
-#undef VCR_SDPA_LAUNCH
-  if (nsplit > 1 && pv) {
-    const long grows = (long)ng * a->nbatch * a->nq;
-    hipLaunchKernelGGL(sdpa_merge_kernel, dim3((unsigned)((grows + 3) / 4)), dim3(256), 0, s, a->split_work, nsplit, ng, a->nbatch, a->heads,
-                       a->nq, a->ldo, a->out, ng > 1 ? a->out_group_stride : 0L);
-  } else if (nsplit > 1) {
-    const long rows = (long)a->nbatch * a->heads * a->nq;
-    hipLaunchKernelGGL(rowstat_merge_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, a->split_work, nsplit, rows, a->rowstat);
-  }
+  const bool persist = a->variant != 1 && fast && nsplit == 1 && blocks >= 2 * slots;
+  const long rows = pv ? (long)ng * a->nbatch * a->nq : (long)a->nbatch * a->heads * a->nq;   // (group, batch, query) / (batch, head, query)
+  *p = SdpaPlan{persist, a->key_keep != nullptr, pv, nsplit, (int)blocks, dim3((unsigned)(persist ? slots : blocks * nsplit)), dim3(256),
+                (int)(2 * sizeof(Stage) + (a->key_index ? ((a->nk * 4 + 15) & ~15) : 0)),
+                nsplit == 1 ? SdpaMerge::none : pv ? SdpaMerge::output : SdpaMerge::rowstat, rows,
+                dim3((unsigned)(pv ? (rows + 3) / 4 : (rows + 255) / 256))};
+  return VCR_OK;
+}
+
+}  // namespace
+
+extern "C" int vcr_keymass_f32(const vcr_keymass_args* a, vcr_stream_t stream) {
+  if (!a || !a->score || !a->rowstat || !a->mass) return VCR_EINVAL;
+  if (a->nbatch <= 0 || a->heads <= 0 || a->nq <= 0 || a->nk <= 0 || a->ld < a->nk) return VCR_EINVAL;
+  // 16 B per lane when every row is 16-B aligned and padded to a multiple of 4 keys (vcr_sdpa_f32's score_out is)
+  if ((a->ld & 3) == 0 && (((uintptr_t)a->score) & 15) == 0 && ((a->nk + 3) & ~3) <= a->ld)
+    hipLaunchKernelGGL(keymass4_kernel, dim3((a->nk + 255) / 256, a->nbatch), dim3(64 * KM_WAVES), 0, (hipStream_t)stream, *a);
+  else
+    hipLaunchKernelGGL(keymass_kernel, dim3((a->nk + 63) / 64, a->nbatch), dim3(256), 0, (hipStream_t)stream, *a);
   return VCR_LAUNCH_RC();
+}
+
+extern "C" int vcr_sdpa_f32(const vcr_sdpa_args* a, vcr_stream_t stream) {
+  vcr_stream_scope bound(stream);
+  SdpaPlan p;
+  int rc = sdpa_plan(a, &p);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (p.persist) rc = vcr_launch<sdpa_persist_kernel>(p.grid, p.block, p.lds, s, *a, p.nitems);
+  else if (p.mask) rc = p.pv ? vcr_launch<sdpa_kernel<true, true>>(p.grid, p.block, p.lds, s, *a, p.nsplit)
+                             : vcr_launch<sdpa_kernel<true, false>>(p.grid, p.block, p.lds, s, *a, p.nsplit);
+  else rc = p.pv ? vcr_launch<sdpa_kernel<false, true>>(p.grid, p.block, p.lds, s, *a, p.nsplit)
+                 : vcr_launch<sdpa_kernel<false, false>>(p.grid, p.block, p.lds, s, *a, p.nsplit);
+  if (rc || p.merge == SdpaMerge::none) return rc;
+  const int ng = a->ngroups > 1 ? a->ngroups : 1;
+  if (p.merge == SdpaMerge::output)
+    hipLaunchKernelGGL(sdpa_merge_kernel, p.merge_grid, dim3(256), 0, s, a->split_work, p.nsplit, ng, a->nbatch, a->heads, a->nq, a->ldo,
+                       a->out, ng > 1 ? a->out_group_stride : 0L);
+  else
+    hipLaunchKernelGGL(rowstat_merge_kernel, p.merge_grid, dim3(256), 0, s, a->split_work, p.nsplit, p.rows, a->rowstat);
+  return VCR_LAUNCH_RC();
+}
+
+// Host-only, library-internal (forward.hip): sdpa_plan's return code for a launch, its key split and whether the persistent
+// kernel takes it (on the current device, as the launch would).
+extern "C" int vcr_sdpa_forms_(const vcr_sdpa_args* a, int* nsplit, int* persistent) {
+  SdpaPlan p;
+  const int e = sdpa_plan(a, &p);
+  if (!e && nsplit) *nsplit = p.nsplit;
+  if (!e && persistent) *persistent = p.persist;
+  return e;
+}
+
+// Host-only, library-internal (forward.hip carve()): floats of vcr_sdpa_args.split_work for attention-output launches of up to
+// `rows` query rows (groups x batches x queries), `heads` heads and output pitch `ldo` on `cus` CUs -- the planes up to the cap
+// and the (max, sum) records; none when even the smallest launch (nbatch x nq queries) fills more than half a round.
+extern "C" long vcr_sdpa_split_floats_(size_t rows, int heads, int ldo, long nbatch, int nq, int cus) {
+  if (sdpa_blocks(nq, heads, nbatch) * 2 > (long)cus * SDPA_WG_PER_CU) return 0;
+  const size_t want = (size_t)VCR_SDPA_MAX_SPLIT * rows * ldo, cap = SDPA_PLANE_CAP / 4;
+  return (long)((want < cap ? want : cap) + (size_t)VCR_SDPA_MAX_SPLIT * rows * heads * 2);
 }

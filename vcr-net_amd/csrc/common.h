@@ -62,6 +62,14 @@ inline void vcr_raise_dyn_lds(const void* kernel, int bytes, vcr_lds_cache& c) {
     static vcr_lds_cache vcr_lds_cache_;                                             \
     vcr_raise_dyn_lds(reinterpret_cast<const void*>(kernel), (bytes), vcr_lds_cache_); \
   } while (0)
+// One launch with `lds` bytes of dynamic LDS, the limit raised first (one cache per kernel: Kernel is a template argument);
+// returns the launch's error code.
+template <auto Kernel, class... Args>
+int vcr_launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... a) {
+  VCR_DYN_LDS(Kernel, (int)lds);
+  hipLaunchKernelGGL(Kernel, grid, block, lds, s, a...);
+  return VCR_LAUNCH_RC();
+}
 #define VCR_NEG_INF (-__builtin_huge_valf())
 
 // v_mfma_f32_32x32x2_f32: lane l supplies A[i = l&31][k = l>>5] and B[k = l>>5][j = l&31];
@@ -127,10 +135,6 @@ struct vcr_stream_scope {                                 // first statement of 
   }
   ~vcr_stream_scope() { vcr_bound_device() = saved; }
 };
-// vcr_sdpa_f32: rows of a query block, resident workgroups per CU of its kernels -- shared with the forward's workspace plan
-// (forward.hip carve(): the key-split planes are only set aside where the launcher can take a split)
-constexpr int VCR_SDPA_QROWS = 128;
-constexpr int VCR_SDPA_WG_PER_CU = 2;
 inline int vcr_cu_count() {
   static std::atomic<int> cache[16];
   int dev = vcr_bound_device();

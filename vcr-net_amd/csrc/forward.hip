@@ -116,6 +116,11 @@ inline int merged_encdec(const vcr_vcrnet_weights* W) {
          W->fold_encdec_qkv.bias;
 }
 
+extern "C" int vcr_linear_shapes_(const vcr_linear_args* a, const vcr_linear_args* b, int* shape_a, int* shape_b);   // linear.hip
+extern "C" int vcr_knn_forms_(const vcr_knn_args* a, const vcr_knn_args* b, int* ordered, int* inline_a, int* inline_b);  // knn.hip
+extern "C" int vcr_sdpa_forms_(const vcr_sdpa_args* a, int* nsplit, int* persistent);   // attention.hip
+extern "C" long vcr_sdpa_split_floats_(size_t rows, int heads, int ldo, long nbatch, int nq, int cus);   // attention.hip
+
 // Every workspace address of a forward.  cus: the CU count of the device the attention launches plan their key split for.
 // pass: forward_impl's (a vcrnetIter pass with target reuse finds emb, d1, qc and kvc behind the plan).
 Ws carve(void* base, const vcr_vcrnet_weights* W, int B, int N, int cus, int pass = 0) {
@@ -152,18 +157,10 @@ Ws carve(void* base, const vcr_vcrnet_weights* W, int B, int N, int cus, int pas
   pl.want(w.embf, M * E, DEC_NORM, END);  pl.want(w.side4, M * 4, DEC_NORM, END);
   pl.want(w.csplit, VCR_PAIRSCORE_MAX_SPLIT * (M / 2) * 8, HEAD, END);   // vcr_softcorr_args.split_work of the soft heads
   pl.want(w.corr_ba, (size_t)B * N * 4, HEAD2, END);
-  {
-    // planes of a key-split attention-output launch (vcr_sdpa_args.split_work; the grouped self-attention has 2 M rows):
-    // the library only splits while the planes stay below 64 MB, i.e. at small batches -- no more than that is set aside
-    const size_t rows = 2 * M, ml = (size_t)VCR_SDPA_MAX_SPLIT * rows * heads * 2;
-    const size_t want = (size_t)VCR_SDPA_MAX_SPLIT * rows * E, cap = ((size_t)64 << 20) / 4;
-    w.asplit_floats = (long)((want < cap ? want : cap) + ml);
-    // ... and only for grids of at most half a round: vcr_sdpa_f32 splits the keys when blocks x split <= slots (the same
-    // constants and CU count as its launcher; 512 slots on MI355X); the smallest attention-output launch of the forward is the
-    // cross-attention (ceil(N / 128) x 2B x heads blocks)
-    if ((long)((N + VCR_SDPA_QROWS - 1) / VCR_SDPA_QROWS) * 2 * B * heads * 2 > (long)cus * VCR_SDPA_WG_PER_CU) w.asplit_floats = 0;
-    pl.want(w.asplit, (size_t)w.asplit_floats, merged ? ENCDEC_SELF : ENC_SELF, CROSS_ATT);
-  }
+  // planes of the attention-output launches' key split (vcr_sdpa_args.split_work), as far as the library takes one on this many
+  // CUs (small batches only): the grouped self-attention has 2 M rows, the smallest launch is the cross-attention (2 B x N queries)
+  w.asplit_floats = vcr_sdpa_split_floats_(2 * M, heads, E, 2L * B, N, cus);
+  pl.want(w.asplit, (size_t)w.asplit_floats, merged ? ENCDEC_SELF : ENC_SELF, CROSS_ATT);
   const size_t sn = M * (E / 64) * 2;
   pl.want(w.st_emb, sn, CONV3, DEC_QKV);                 // (the merged form's last reader is ENCDEC_QKV)
   pl.want(w.st_e1, sn, merged ? WO_PAIR : ENC_WO, merged ? FFN1_CROSS_Q : ENC_FFN1);
@@ -235,8 +232,6 @@ __global__ __launch_bounds__(256) void zero_i32_kernel(int32_t* p, long n) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i < n) p[i] = 0;
 }
-extern "C" int vcr_linear_shapes_(const vcr_linear_args* a, const vcr_linear_args* b, int* shape_a, int* shape_b);   // linear.hip
-extern "C" int vcr_knn_forms_(const vcr_knn_args* a, const vcr_knn_args* b, int* ordered, int* inline_a, int* inline_b);  // knn.hip
 
 struct Runner {
   hipStream_t stream; vcr_trace* tr; int rc = 0;
@@ -428,12 +423,11 @@ struct Runner {
       // free until the FFN and holds it when F >= 2E), else the masked form
       if (!io->force_keys) rank("select:dec.cross.keys", w.keymass, 1, nb, N, nkeep, w.xorder, w.keep, 1);
       if (io->out_keys) copy_idx("select:dec.cross.keys.out", io->out_keys, w.xorder, (size_t)nb * nkeep);
-      if (!sdpa_split && nkeep <= 16384) {               // (vcr_sdpa_f32 holds the index list in LDS: <= 16 384 kept keys;
-        run("sdpa:dec.cross", [&] {                      //  longer lists take the dense copy / the masked form below)
-          vcr_sdpa_args a{w.qc, E, w.kvc, 2 * E, w.kvc + E, 2 * E, w.attx, E, nb, H, N, nkeep, 1.0f / sqrtf(128.f), B};
-          a.key_index = w.xorder; a.nk_src = N;
-          return vcr_sdpa_f32(&a, stream);
-        });
+      vcr_sdpa_args xa{w.qc, E, w.kvc, 2 * E, w.kvc + E, 2 * E, w.attx, E, nb, H, N, nkeep, 1.0f / sqrtf(128.f), B};
+      xa.key_index = w.xorder; xa.nk_src = N;
+      // (vcr_sdpa_f32 holds the index list in LDS: a list it refuses takes the dense copy / the masked form below)
+      if (!sdpa_split && vcr_sdpa_forms_(&xa, nullptr, nullptr) == VCR_OK) {
+        run("sdpa:dec.cross", [&] { return vcr_sdpa_f32(&xa, stream); });
         return;
       }
       if (W->F >= 2 * E) {

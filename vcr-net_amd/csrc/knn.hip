@@ -1599,13 +1599,6 @@ __global__ __launch_bounds__(256) void knn_tiebreak2_kernel(vcr_knn_args a, vcr_
   if (blockIdx.y == 0) tiebreak_body(a); else tiebreak_body(b);
 }
 
-template <auto Kernel, class... Args>
-int launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... a) {
-  VCR_DYN_LDS(Kernel, (int)lds);                         // one cache per kernel: Kernel is a template argument
-  hipLaunchKernelGGL(Kernel, grid, block, lds, s, a...);
-  return VCR_LAUNCH_RC();
-}
-
 }  // namespace
 
 // the tie counter is zeroed by a kernel, not hipMemsetAsync: a memset NODE in a captured HIP graph made replays on the
@@ -1737,15 +1730,15 @@ static int zero_ties(const KnnPlan& p, hipStream_t s) { return p.zero ? zero_cou
 // rows with an exact tie at the (k+1)-th value: replay libstdc++'s selection on them (knn_tiebreak_kernel); b: a second search or NULL
 static int replay(const vcr_knn_args& a, const vcr_knn_args* b, hipStream_t s) {
   const size_t la = tiebreak_launch_lds(a.N), lb = b ? tiebreak_launch_lds(b->N) : 0, lds = la > lb ? la : lb;
-  if (b) return launch<knn_tiebreak2_kernel>(dim3(TB_BLOCKS, 2), dim3(256), lds, s, a, *b);
-  return launch<knn_tiebreak_kernel>(dim3(TB_BLOCKS), dim3(256), lds, s, a);
+  if (b) return vcr_launch<knn_tiebreak2_kernel>(dim3(TB_BLOCKS, 2), dim3(256), lds, s, a, *b);
+  return vcr_launch<knn_tiebreak_kernel>(dim3(TB_BLOCKS), dim3(256), lds, s, a);
 }
 
 // one search: zero the tie counter, search, replay
 static int knn_run(const KnnPlan& p, hipStream_t s) {
   int rc = zero_ties(p, s);
   if (rc) return rc;
-#define VCR_K(...) rc = launch<__VA_ARGS__>(p.grid, p.block, p.lds, s, p.a)
+#define VCR_K(...) rc = vcr_launch<__VA_ARGS__>(p.grid, p.block, p.lds, s, p.a)
   if (p.body == KnnBody::col16 && p.a.C == 4) { if (p.KS == 22) VCR_K(knn3c_kernel<22, 4>); else if (p.KS == 42) VCR_K(knn3c_kernel<42, 4>); else VCR_K(knn3c_kernel<64, 4>); }
   else if (p.body == KnnBody::col16 && p.xt) { if (p.KS == 22) VCR_K(knn64c_kernel<22, 4, true>); else if (p.KS == 42) VCR_K(knn64c_kernel<42, 4, true>); else VCR_K(knn64c_kernel<64, 4, true>); }
   else if (p.body == KnnBody::col16) { if (p.KS == 22) VCR_K(knn64c_kernel<22, 4, false>); else if (p.KS == 42) VCR_K(knn64c_kernel<42, 4, false>); else VCR_K(knn64c_kernel<64, 4, false>); }
@@ -1828,7 +1821,7 @@ extern "C" int vcr_knn_pair_f32(const vcr_knn_args* u64, const vcr_knn_args* u3,
   const dim3 grid(n64 + gx3 * a3.B), block(256);
   const size_t lds = p64.lds > p3.lds ? p64.lds : p3.lds;
   const vcr_knn_args &k64 = p64.a, &k3 = p3.a;
-#define VCR_KP(...) rc = launch<__VA_ARGS__>(grid, block, lds, s, k64, k3, n64, gx64, gx3)
+#define VCR_KP(...) rc = vcr_launch<__VA_ARGS__>(grid, block, lds, s, k64, k3, n64, gx64, gx3)
   if (form == PairForm::small) {
     if (p64.S == 4) { if (p3.S == 4) VCR_KP(knn_pair_small_kernel<22, 4, 4>); else if (p3.S == 2) VCR_KP(knn_pair_small_kernel<22, 4, 2>); else VCR_KP(knn_pair_small_kernel<22, 4, 1>); }
     else { if (p3.S == 4) VCR_KP(knn_pair_small_kernel<22, 2, 4>); else if (p3.S == 2) VCR_KP(knn_pair_small_kernel<22, 2, 2>); else VCR_KP(knn_pair_small_kernel<22, 2, 1>); }

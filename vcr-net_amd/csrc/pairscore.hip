@@ -359,8 +359,16 @@ __global__ __launch_bounds__(256) void score_rowpass_kernel(vcr_scoremass_args p
   if (lane == 0) p.row_mass[(size_t)b * p.n_rows + i] = acc;
 }
 
-int launch(const vcr_pairscore_args* a, vcr_stream_t stream) {
-  vcr_stream_scope bound(stream);
+// How one pair-score launch runs.  pairscore_plan() decides it from the arguments, and it is the only place that does.
+enum class PsMerge { none, corr, stat };                 // after a split of the streamed side: corrmerge / statmerge
+struct PairscorePlan {
+  int op, ot;                // pairscore_kernel<op, ot>: owner tiles (of 32) per block
+  int nsplit;                // runs of streamed tiles per owner block (1: none)
+  dim3 grid, block; int lds;
+  PsMerge merge; long rows; dim3 merge_grid;             // the merge and the (batch, owner) rows it combines
+};
+
+int pairscore_plan(const vcr_pairscore_args* a, PairscorePlan* p) {
   if (!a || !a->own || !a->str) return VCR_EINVAL;
   if (a->nbatch <= 0 || a->n_own <= 0 || a->n_str <= 0 || a->E <= 0 || (a->E % 128) || a->E > 1024) return VCR_EINVAL;
   if ((a->ld_own & 3) || (a->ld_str & 3) || a->ld_own < a->E || a->ld_str < a->E) return VCR_EINVAL;
@@ -394,28 +402,29 @@ int launch(const vcr_pairscore_args* a, vcr_stream_t stream) {
       if (c < 0.8 * base && c < best - 1e-9) { best = c; nsplit = sp; }
     }
   }
-  dim3 grid(owner_blocks * nsplit, a->nbatch);
-  hipStream_t s = (hipStream_t)stream;
-#define VCR_PS_LAUNCH(OPV, OTV)                                                                                         \
-  do {                                                                                                                   \
-    VCR_DYN_LDS((pairscore_kernel<OPV, OTV>), lds);                                                                      \
-    hipLaunchKernelGGL((pairscore_kernel<OPV, OTV>), grid, dim3(256 * OTV), lds, s, *a, nsplit);                        \
-  } while (0)
-  if (ot == 2) { if (a->op == 0) VCR_PS_LAUNCH(0, 2); else if (a->op == 1) VCR_PS_LAUNCH(1, 2); else VCR_PS_LAUNCH(2, 2); }
-  else         { if (a->op == 0) VCR_PS_LAUNCH(0, 1); else if (a->op == 1) VCR_PS_LAUNCH(1, 1); else VCR_PS_LAUNCH(2, 1); }
-#undef VCR_PS_LAUNCH
-  if (nsplit > 1) {
-    const long rows = (long)a->nbatch * a->n_own;
-    const dim3 mg((unsigned)((rows + 255) / 256));
-    if (a->op == 0) hipLaunchKernelGGL(corrmerge_kernel, mg, dim3(256), 0, s, a->split_work, nsplit, rows, a->corr4);
-    else hipLaunchKernelGGL(statmerge_kernel, mg, dim3(256), 0, s, a->split_work, nsplit, rows, a->stat2);
-  }
-  return VCR_LAUNCH_RC();
+  const long rows = (long)a->nbatch * a->n_own;
+  *p = PairscorePlan{a->op, ot, nsplit, dim3(owner_blocks * nsplit, a->nbatch), dim3(256 * ot), lds,
+                     nsplit == 1 ? PsMerge::none : a->op == 0 ? PsMerge::corr : PsMerge::stat, rows, dim3((unsigned)((rows + 255) / 256))};
+  return VCR_OK;
 }
 
 }  // namespace
 
-extern "C" int vcr_pairscore_f32(const vcr_pairscore_args* a, vcr_stream_t stream) { return launch(a, stream); }
+extern "C" int vcr_pairscore_f32(const vcr_pairscore_args* a, vcr_stream_t stream) {
+  vcr_stream_scope bound(stream);
+  PairscorePlan p;
+  int rc = pairscore_plan(a, &p);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+#define VCR_PS(OP, OT) rc = vcr_launch<pairscore_kernel<OP, OT>>(p.grid, p.block, p.lds, s, *a, p.nsplit)
+  if (p.ot == 2) { if (p.op == 0) VCR_PS(0, 2); else if (p.op == 1) VCR_PS(1, 2); else VCR_PS(2, 2); }
+  else           { if (p.op == 0) VCR_PS(0, 1); else if (p.op == 1) VCR_PS(1, 1); else VCR_PS(2, 1); }
+#undef VCR_PS
+  if (rc || p.merge == PsMerge::none) return rc;
+  if (p.merge == PsMerge::corr) hipLaunchKernelGGL(corrmerge_kernel, p.merge_grid, dim3(256), 0, s, a->split_work, p.nsplit, p.rows, a->corr4);
+  else hipLaunchKernelGGL(statmerge_kernel, p.merge_grid, dim3(256), 0, s, a->split_work, p.nsplit, p.rows, a->stat2);
+  return VCR_LAUNCH_RC();
+}
 
 extern "C" int vcr_scoremass_f32(const vcr_scoremass_args* a, vcr_stream_t stream) {
   if (!a || !a->score || !a->row_stat2 || !a->col_stat2 || !a->col_mass || !a->row_mass) return VCR_EINVAL;
@@ -435,5 +444,5 @@ extern "C" int vcr_softcorr_f32(const vcr_softcorr_args* a, vcr_stream_t stream)
   p.nbatch = a->nbatch; p.n_own = a->nq; p.n_str = a->nk; p.E = a->E;
   p.score = a->mode; p.scale = a->scale; p.str_batch_shift = 0; p.op = 0; p.corr4 = a->corr4;
   p.split_work = a->split_work; p.split_work_floats = a->split_work_floats;
-  return launch(&p, stream);
+  return vcr_pairscore_f32(&p, stream);
 }
