@@ -485,6 +485,37 @@ typedef struct {
 } vcr_make_pairs_args;
 int vcr_make_pairs_f32(const vcr_make_pairs_args*, vcr_stream_t);
 
+/* ---- farthest-point sampling (farthest_point_sample, util/util.py:107-140): npoint points of every cloud, each the one
+ * farthest from those already chosen, as ONE launch whatever npoint is (the rounds run inside the kernel).
+ *   start  : the first point per cloud, or (start == NULL) the reference's rule: the point farthest from the barycentre
+ *            (coordinate sums accumulated in fp64 and rounded once, then c = sum / N in fp32);
+ *   round i: idx[i] = far;  d_n = (dx*dx + dy*dy) + dz*dz with dx = x_n - x_far ... (every operation rounded, no fma);
+ *            dist_n = d_n where d_n < dist_n (dist starts at 1e10);  far = the LOWEST n with the largest dist_n.
+ * The indices are the reference's index for index (torch.max's first-maximum rule; NaN above +inf in the barycentre rule);
+ * npoint > N repeats points as the reference does.  Non-finite coordinates need no special case: a point with a NaN / inf
+ * coordinate keeps dist = 1e10, is chosen second and then for ever -- every index written is in [0, N) whatever the values.
+ * xyz_cf [B,3,N] channels-first, cloud b at xyz_cf + b * cloud_stride (floats; >= 3 N).  idx [B,npoint] int32.
+ * out_cf (optional) [B,3,npoint] channels-first: the sampled clouds, written by the same launch as each point is chosen --
+ * they feed vcr_vcrnet_forward_f32 with no gather launch.  start (optional) [B] int32 on the DEVICE: values outside
+ * [0, N) are clamped by the kernel.  One workgroup per cloud; N <= 131 072 and B * max(N, npoint) < 2^31, VCR_EUNSUPPORTED
+ * beyond.  variant: tuning / tests, never changes a result.  0 = chosen from N: 1 = the resident form (coordinates and
+ * distances in registers, loaded once: N <= 20 480, VCR_EUNSUPPORTED beyond); 2 = the streaming form (coordinates re-read
+ * from L2 every round, distances in registers and LDS: any N).  Any other value: VCR_EINVAL. */
+typedef struct {
+  uint32_t struct_bytes;              /* sizeof(vcr_fps_args) as the CALLER was compiled (see vcr_knn_args); the mandatory part
+                                         ends behind idx: 0, shorter than that or longer than this library knows: VCR_EINVAL */
+  const float* xyz_cf; long cloud_stride;
+  int B, N, npoint;
+  const int32_t* start;
+  int32_t* idx;
+  float* out_cf;
+  int variant;
+} vcr_fps_args;
+int vcr_fps_f32(const vcr_fps_args*, vcr_stream_t);
+/* Host-only query (nothing is launched, no device needed): the form vcr_fps_f32 would run for these arguments (1 resident,
+ * 2 streaming) and the points each of the workgroup's 1024 threads holds; returns VCR_OK or the VCR_E* code of the call. */
+int vcr_fps_form(const vcr_fps_args*, int* form, int* points_per_thread);
+
 /* ---- whole forward: VCRNet.forward (vcrnet_model.py:495-518), LPDNet + Transformer + VcpTopK(whole)/
  * VcpByDis + SVD, both clouds batched as 2B.  Weight pointers are the packed device tensors the host
  * module prepares once; all [N,K] row-major. */

@@ -11,4 +11,15 @@ the repository root).
 """
 from . import weights, synth  # noqa: F401
 
-__all__ = ["weights", "synth"]
+__all__ = ["weights", "synth", "farthest_point_sample", "register_sampled"]
+
+
+def __getattr__(name):
+    # resolved on first use: native / module load the HIP library's bindings, which `import vcrnet_amd` alone does not need
+    if name == "farthest_point_sample":
+        from .native import farthest_point_sample
+        return farthest_point_sample
+    if name == "register_sampled":
+        from .module import register_sampled
+        return register_sampled
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

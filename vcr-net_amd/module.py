@@ -746,3 +746,26 @@ def vcrnetIter(net, src, tgt, iter=1):
         # util/util.py:91-96 and vcrnet_model.py:35-41 as one vcr_pose_step_f32 launch (the device loop's own kernel)
         cur, R_f, t_f, R_ba, t_ba = native.pose_step(R.detach(), t.detach(), cur, R_f, t_f)
     return srcK, corrK, R_f, t_f, R_ba, t_ba
+
+
+def register_sampled(net, src, tgt, npoint, iter=1, start=None):
+    """Register two clouds of ANY size: src [B,3,Ns] and tgt [B,3,Nt] (Ns != Nt allowed, each up to 131 072 points) are reduced
+    to ``npoint`` points each by farthest-point sampling on the device (two vcr_fps_f32 launches, the reference's
+    farthest_point_sample index for index), and ``vcrnetIter(net, src_s, tgt_s, iter)`` runs on the sampled clouds.  The
+    samples are subsets of the clouds, so the pose returned is the pose of the full clouds.
+    ``start``: None = the reference's start (the point farthest from the barycentre), or a pair (start_src, start_tgt) of
+    int [B] first points.  Returns (srcK, src_corrK, R_ab, t_ab, R_ba, t_ba, idx_src, idx_tgt), idx_* int64 [B, npoint]."""
+    for name, x in (("src", src), ("tgt", tgt)):
+        if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != 3:
+            raise native.VcrHipError(f"register_sampled: {name} must be a [B, 3, N] point cloud, got "
+                                     f"{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+    if src.shape[0] != tgt.shape[0]:
+        raise native.VcrHipError(f"register_sampled: src and tgt must hold the same number of clouds, got {src.shape[0]} "
+                                 f"and {tgt.shape[0]}")
+    if not (src.is_cuda and tgt.is_cuda):
+        raise native.VcrHipError("register_sampled runs on the MI355X HIP path only; move the clouds to cuda "
+                                 "(there is no CPU fallback by design)")
+    s_src, s_tgt = (None, None) if start is None else start
+    idx_s, src_s = native.fps(src.float(), npoint, start=s_src)
+    idx_t, tgt_s = native.fps(tgt.float(), npoint, start=s_tgt)
+    return tuple(vcrnetIter(net, src_s, tgt_s, iter)) + (idx_s.long(), idx_t.long())

@@ -50,6 +50,11 @@ class KnnOrderArgs(C.Structure):
                 ("cen64_sqmax", f32p), ("ord_ok", f32p), ("ord_stat", f32p), ("guard_ratio", C.c_float)]
 
 
+class FpsArgs(_Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("xyz_cf", f32p), ("cloud_stride", C.c_long), ("B", C.c_int), ("N", C.c_int),
+                ("npoint", C.c_int), ("start", f32p), ("idx", f32p), ("out_cf", f32p), ("variant", C.c_int)]
+
+
 class LinearArgs(C.Structure):
     _fields_ = [("x", f32p), ("ldx", C.c_int), ("w", f32p), ("bias", f32p), ("residual", f32p), ("ldr", C.c_int),
                 ("y", f32p), ("ldy", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("relu", C.c_int),
@@ -229,6 +234,7 @@ _SIGS = {
     "vcr_rigid_svd_f32": RigidSvdArgs, "vcr_pairscore_f32": PairscoreArgs, "vcr_rankselect_f32": RankselectArgs,
     "vcr_gather_rows_f32": GatherArgs, "vcr_scoremass_f32": ScoremassArgs, "vcr_keymass_f32": KeymassArgs, "vcr_make_pairs_f32": MakePairsArgs,
     "vcr_edgerows_f32": EdgerowsArgs, "vcr_segmax_f32": SegmaxArgs, "vcr_edgechain_f32": EdgechainArgs,
+    "vcr_fps_f32": FpsArgs,
 }
 
 _lib: Optional[C.CDLL] = None
@@ -272,6 +278,8 @@ def lib() -> C.CDLL:
         L.vcr_vcrnet_iter_f32.argtypes = [C.POINTER(VcrnetWeights), C.POINTER(VcrnetIo), C.c_int, C.c_void_p,
                                           C.c_size_t, C.c_void_p, C.POINTER(Trace)]
         L.vcr_vcrnet_iter_f32.restype = C.c_int
+        L.vcr_fps_form.argtypes = [C.POINTER(FpsArgs), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.vcr_fps_form.restype = C.c_int
         L.vcr_event_create.argtypes = [C.POINTER(C.c_void_p)]; L.vcr_event_create.restype = C.c_int
         L.vcr_event_destroy.argtypes = [C.c_void_p]; L.vcr_event_destroy.restype = C.c_int
         L.vcr_event_record.argtypes = [C.c_void_p, C.c_void_p]; L.vcr_event_record.restype = C.c_int
@@ -717,6 +725,48 @@ def make_pairs(cloud, R_ab, t_ab, pick, perm_src, perm_tgt, keep):
     call("vcr_make_pairs_f32", MakePairsArgs(ptr(cloud), P, ptr(R_ab), ptr(t_ab), ptr(pick), ptr(perm_src),
                                              ptr(perm_tgt), B, N, keep, ptr(src), ptr(tgt)))
     return src, tgt
+
+
+FPS_FORMS = {"resident": 1, "streaming": 2}           # vcr_fps_args.variant (0 = chosen from N)
+
+
+def fps_form(N, npoint=1, B=1, variant=0):
+    """vcr_fps_form (host only): (form, points per thread) vcr_fps_f32 would run a [B, 3, N] cloud with -- form 1 resident,
+    2 streaming."""
+    a = FpsArgs(0x1000, 3 * N, B, N, npoint, None, 0x2000, None, variant)   # (never dereferenced on the host)
+    form, ppt = C.c_int(0), C.c_int(0)
+    check(lib().vcr_fps_form(C.byref(a), C.byref(form), C.byref(ppt)), "vcr_fps_form")
+    return form.value, ppt.value
+
+
+@_guarded
+def fps(xyz, npoint, start=None, want_points=True, variant=0, prefill=None):
+    """vcr_fps_f32: farthest-point sampling of xyz [B,3,N] fp32 (channels-first; a batch stride above 3 N is read in place)
+    -> (idx int32 [B,npoint], the sampled clouds [B,3,npoint] or None).  start: None = the reference's rule (the point
+    farthest from the barycentre), or int [B] first points (the kernel clamps them into [0, N)).  variant: 0 automatic,
+    1 / 2 force the resident / streaming form (same indices).  prefill: a value idx holds before the launch."""
+    if xyz.dim() != 3 or xyz.shape[1] != 3 or xyz.dtype != torch.float32:
+        raise VcrHipError(f"fps: xyz must be a [B, 3, N] float32 cloud, got {tuple(xyz.shape)} {xyz.dtype}")
+    B, _, N = xyz.shape
+    if N >= 1 and not (xyz.stride(2) == 1 and xyz.stride(1) == N and (B == 1 or xyz.stride(0) >= 3 * N)):
+        xyz = xyz.contiguous()
+    stride = xyz.stride(0) if B > 1 else 3 * N
+    idx = _i32(B, int(npoint), device=xyz.device, prefill=prefill)
+    pts = _f32(B, 3, int(npoint), device=xyz.device) if want_points else None
+    if start is not None:
+        start = start.to(device=xyz.device, dtype=torch.int32).contiguous()
+        if start.numel() != B:
+            raise VcrHipError(f"fps: start must hold one index per cloud ({B}), got {tuple(start.shape)}")
+    call("vcr_fps_f32", FpsArgs(ptr(xyz), stride, B, N, int(npoint), ptr(start), ptr(idx), ptr(pts), int(variant)))
+    return idx, pts
+
+
+def farthest_point_sample(xyz, npoint):
+    """The reference's farthest_point_sample(xyz[B,3,N], npoint) (util/util.py:107-140): int64 [B, npoint] indices, the first
+    the point farthest from the barycentre.  Device tensors only."""
+    if not xyz.is_cuda:
+        raise VcrHipError("farthest_point_sample runs on the HIP path only; move xyz to cuda (there is no CPU fallback)")
+    return fps(xyz.float(), npoint, want_points=False)[0].long()
 
 
 class IcpArgs(C.Structure):
