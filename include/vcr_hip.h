@@ -198,22 +198,26 @@ typedef struct {
    * atomic max -- needs relu != 0 (values >= 0) and segmax_out pre-set to 0 (vcr_edgerows_f32 does that).  y may then
    * be NULL: the per-edge activations of the last conv are never written.  LDS-DMA kernels (variant 0) only. */
   float* segmax_out; int ld_segmax; int seg_k;
-  int variant;                        /* tuning / tests, 0 = automatic (LDS-DMA staging, one 128x128 tile per workgroup:
-                                         BK 16, 32x32x2 MFMAs and four workgroups per CU without a residual; BK 32 and
-                                         16x16x4 MFMAs with one -- those on 96x128 tiles when M-tiles of 128 rows
-                                         would leave a mostly empty last round of workgroups on the 256 CUs, e.g.
-                                         M = 36 864 at BASELINE configs[2]).
-                                         bit11 (2048) force 96-row tiles (16x16x4 MFMAs; not with bit10 / bit2:
-                                         VCR_EINVAL), bit12 (4096) force 128-row tiles: the tile height does not change
-                                         a shape's results; bit13 (8192) / bit14 (16384) force 64- / 32-row tiles (BK 32,
+  int variant;                        /* tuning / tests: VCR_LINEAR_* bits below, 0 = automatic (LDS-DMA staging, one 128x128
+                                         tile per workgroup: BK 16, 32x32x2 MFMAs and four workgroups per CU without a
+                                         residual; BK 32 and 16x16x4 MFMAs with one -- those on 96x128 tiles when M-tiles
+                                         of 128 rows would leave a mostly empty last round of workgroups on the 256 CUs,
+                                         e.g. M = 36 864 at BASELINE configs[2]).
+                                         _ROWS96 forces 96-row tiles (16x16x4 MFMAs; not with _MFMA32 / _REGSTAGE:
+                                         VCR_EINVAL), _ROWS128 forces 128-row tiles: the tile height does not change
+                                         a shape's results; _ROWS64 / _ROWS32 force 64- / 32-row tiles (BK 32,
                                          16x16x4 MFMAs; taken automatically, with variant == 0, by launches of far less
                                          than one round of workgroups -- one or two pairs per call);
-                                         bit3 (8) force BK 32, bit6 (64) force BK 16; bit4 (16) force the 16x16x4 MFMA
-                                         shape, bit10 (1024) force 32x32x2; bit2 (4) the register-staged kernel without
+                                         _BK32 forces BK 32, _BK16 forces BK 16; _MFMA16 forces the 16x16x4 MFMA
+                                         shape, _MFMA32 forces 32x32x2; _REGSTAGE the register-staged kernel without
                                          alignment requirements on y / bias / residual (taken automatically when they
                                          are not 16-B aligned).  BK and staging do not change results; the two MFMA shapes
                                          sum k in different orders (fp32-rounding apart).  Any other bit: VCR_EINVAL. */
 } vcr_linear_args;
+enum {                                /* vcr_linear_args.variant (bits 2, 3, 4, 6, 10 - 14) */
+  VCR_LINEAR_REGSTAGE = 4, VCR_LINEAR_BK32 = 8, VCR_LINEAR_MFMA16 = 16, VCR_LINEAR_BK16 = 64, VCR_LINEAR_MFMA32 = 1024,
+  VCR_LINEAR_ROWS96 = 2048, VCR_LINEAR_ROWS128 = 4096, VCR_LINEAR_ROWS64 = 8192, VCR_LINEAR_ROWS32 = 16384
+};
 int vcr_linear_f32(const vcr_linear_args*, vcr_stream_t);
 /* Host-only query (nothing is launched, no device needed): the kernel configuration vcr_linear_f32 would pick for these
  * arguments -- tile rows | k-slab << 8 | (16x16x4 MFMAs ? 1 << 16 : 0) | (LDS-DMA kernel ? 1 << 17 : 0) -- or a negative

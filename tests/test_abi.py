@@ -324,6 +324,54 @@ def test_sdpa_launch_form_of_the_quoted_shapes(lib):
     assert form(2, 1024, 16385, key_index=True)[0] == -1
 
 
+def test_linear_pair_launch_form_of_the_quoted_shapes(lib):
+    """vcr_linear_forms_ (host-only, library-internal): what linear_plan makes of the paired linear launches DESIGN and the
+    tests quote, on 256 CUs -- whether the two halves are one launch, and per half (LDS-DMA family, tile rows, k-slab, MFMA
+    shape, grid[, dynamic LDS bytes]).  K = 512; "res" = a residual and stats_out on that half."""
+    from vcrnet_amd import native
+    lib.vcr_linear_forms_.argtypes = [ctypes.POINTER(native.LinearArgs)] * 2 + [ctypes.POINTER(ctypes.c_int)] * 3
+    lib.vcr_linear_forms_.restype = ctypes.c_int
+
+    def half(M, N, res=False, stats=None, variant=0):
+        a = native.LinearArgs()
+        a.x, a.w, a.y, a.bias = 0x1000, 0x2000, 0x3000, 0x4000            # (never dereferenced on the host)
+        a.ldx, a.ldy, a.M, a.N, a.K, a.variant = 512, N, M, N, 512, variant
+        if res:
+            a.residual, a.ldr = 0x5000, N
+        if res if stats is None else stats:
+            a.stats_out = 0x6000
+        return a
+
+    def forms(a, b=None, lds=True):
+        one, fa, fb = ctypes.c_int(-1), (ctypes.c_int * 8)(), (ctypes.c_int * 8)()
+        assert lib.vcr_linear_forms_(ctypes.byref(a), ctypes.byref(b) if b is not None else None, ctypes.byref(one), fa, fb) == 0
+
+        def short(f):                                            # (family, rows, k-slab, shape, grid[, LDS])
+            return (f[0], f[1], f[2], f[3], f[4] * f[5]) + ((f[6],) if lds else ())
+        return (one.value, short(fa), short(fb)) if b is not None else short(fa)
+    res = lambda M, N=512, **kw: half(M, N, res=True, **kw)      # noqa: E731
+    # configs[1] / configs[2]: the encoder's and the decoder's output projections side by side
+    assert forms(res(32768), res(32768)) == (1, (1, 128, 32, 16, 1024, 65536), (1, 128, 32, 16, 1024, 65536))
+    assert forms(res(36864), res(36864)) == (1, (1, 96, 32, 16, 1536, 57344), (1, 96, 32, 16, 1536, 57344))
+    # configs[1] ffn1 | cross.q: one launch on the BK 16 kernel ... whose second half, alone, takes the one-round rule
+    assert forms(half(32768, 1024), half(16384, 512)) == (1, (1, 128, 16, 32, 2048, 34816), (1, 128, 16, 32, 512, 34816))
+    assert forms(half(16384, 512), lds=False) == (1, 128, 32, 16, 512)
+    # a residual beside none: two launches, the second as it goes alone (the one-round rule)
+    assert forms(res(32768), half(32768, 512), lds=False) == (0, (1, 128, 32, 16, 1024), (1, 128, 32, 16, 1024))
+    # one pair per call: heights from the combined grid
+    assert forms(res(2048), res(2048)) == (1, (1, 64, 32, 16, 128, 49152), (1, 64, 32, 16, 128, 49152))
+    assert forms(half(2048, 1024), half(1024, 512), lds=False) == (1, (1, 128, 16, 16, 128), (1, 128, 16, 16, 32))
+    assert forms(res(2048), res(32768), lds=False) == (1, (1, 96, 32, 16, 88), (1, 96, 32, 16, 1368))
+    assert forms(res(14336), res(14336), lds=False) == (1, (1, 96, 32, 16, 600), (1, 96, 32, 16, 600))
+    assert forms(res(16384), res(16384), lds=False) == (1, (1, 128, 32, 16, 512), (1, 128, 32, 16, 512))
+    # N = 510: the register-staged fallback (2 x TileT<32> of LDS) beside an LDS-DMA launch -- two launches
+    assert forms(half(3000, 510), half(3000, 512)) == (0, (0, 128, 32, 32, 96, 73728), (1, 64, 32, 16, 188, 49152))
+    # forced heights hold for the pair
+    assert forms(res(3000, variant=2048), res(3077, 256, variant=2048), lds=False) == (1, (1, 96, 32, 16, 128), (1, 96, 32, 16, 66))
+    assert forms(res(3000, variant=8192), half(3077, 256, stats=True, variant=8192), lds=False) == \
+        (1, (1, 64, 32, 16, 188), (1, 64, 32, 16, 98))
+
+
 def test_module_contract_on_cpu():
     """Constructor / state-dict contract of the reference module without a GPU."""
     from types import SimpleNamespace

@@ -116,7 +116,7 @@ inline int merged_encdec(const vcr_vcrnet_weights* W) {
          W->fold_encdec_qkv.bias;
 }
 
-extern "C" int vcr_linear_shapes_(const vcr_linear_args* a, const vcr_linear_args* b, int* shape_a, int* shape_b);   // linear.hip
+extern "C" int vcr_linear_forms_(const vcr_linear_args* a, const vcr_linear_args* b, int* one_launch, int* form_a, int* form_b);   // linear.hip
 extern "C" int vcr_knn_forms_(const vcr_knn_args* a, const vcr_knn_args* b, int* ordered, int* inline_a, int* inline_b);  // knn.hip
 extern "C" int vcr_sdpa_forms_(const vcr_sdpa_args* a, int* nsplit, int* persistent);   // attention.hip
 extern "C" long vcr_sdpa_split_floats_(size_t rows, int heads, int ldo, long nbatch, int nq, int cus);   // attention.hip
@@ -249,13 +249,13 @@ struct Runner {
 
   void pin_shape(vcr_linear_args& a, vcr_linear_args* b = nullptr, int full_rows = 0) {   // full_rows: of the launch this one stands for
     const int fm = full_rows ? full_rows : shape_rows;    // (default: the point rows; DGCNN's per-edge linears pass rows x k)
-    if (!shape_rows || a.M >= fm || (a.variant & (16 | 1024))) return;
+    if (!shape_rows || a.M >= fm || (a.variant & (VCR_LINEAR_MFMA16 | VCR_LINEAR_MFMA32))) return;
     vcr_linear_args fa = a, fb = b ? *b : a;
     fa.M = fm; fb.M = fm;
-    int sa = 0, sb = 0;
-    if (vcr_linear_shapes_(&fa, b ? &fb : nullptr, &sa, &sb) != VCR_OK) return;
-    a.variant |= sa ? 16 : 1024;
-    if (b) b->variant |= sb ? 16 : 1024;
+    int form_a[8], form_b[8];                            // ([3]: the MFMA shape, 16 or 32)
+    if (vcr_linear_forms_(&fa, b ? &fb : nullptr, nullptr, form_a, form_b) != VCR_OK) return;
+    a.variant |= form_a[3] == 16 ? VCR_LINEAR_MFMA16 : VCR_LINEAR_MFMA32;
+    if (b) b->variant |= form_b[3] == 16 ? VCR_LINEAR_MFMA16 : VCR_LINEAR_MFMA32;
   }
   bool ok(int r) { if (rc == 0 && r != 0) rc = r; return rc == 0; }
   // Every launch: none once a launch has failed, else its trace mark (the name -- a string literal: the trace keeps the
@@ -551,8 +551,9 @@ int forward_impl(const vcr_vcrnet_weights* W, const vcr_vcrnet_io* io, void* wor
   R.sdpa_split = W->linear_mode == 2;
   R.sdpa_variant = W->sdpa_variant;
   R.pv_split = w.asplit; R.pv_split_floats = w.asplit_floats;
-  R.linear_variant = (W->linear_mfma == 16 ? 16 : W->linear_mfma == 32 ? 1024 : 0) | (W->linear_bk == 16 ? 64 : W->linear_bk == 32 ? 8 : 0) |
-                     (W->linear_bm == 96 ? 2048 : W->linear_bm == 128 ? 4096 : 0);
+  R.linear_variant = (W->linear_mfma == 16 ? VCR_LINEAR_MFMA16 : W->linear_mfma == 32 ? VCR_LINEAR_MFMA32 : 0) |
+                     (W->linear_bk == 16 ? VCR_LINEAR_BK16 : W->linear_bk == 32 ? VCR_LINEAR_BK32 : 0) |
+                     (W->linear_bm == 96 ? VCR_LINEAR_ROWS96 : W->linear_bm == 128 ? VCR_LINEAR_ROWS128 : 0);
 
   const float* stats_for_ln = W->has_pointer == 1 ? w.st_emb : nullptr;
   if (W->emb_kind == 1) {

@@ -16,6 +16,8 @@
 namespace {
 
 constexpr int BM = 128, BN = 128;
+// resident workgroups per CU of the LDS-DMA kernels at the two k-slabs: their __launch_bounds__, and what the launch planner counts with
+constexpr int LINEAR_WG_PER_CU_BK32 = 2, LINEAR_WG_PER_CU_BK16 = 4;
 // MFMA shape of the LDS-DMA kernels when the call does not force one (vcr_linear_args.variant bits 4 / 10)
 constexpr int LINEAR_MS_DEFAULT = 0;   // 0 = per launch (see vcr_linear_f32), 16 / 32 = that shape everywhere (probe_build.py --set)
 
@@ -527,14 +529,14 @@ __device__ __forceinline__ void linear_glds_body(const vcr_linear_args& p, int t
 }
 
 template <int BK, int MS, int BMV>
-__global__ __launch_bounds__(256, (BK == 32 ? 2 : LINEAR_BLOCKED_ACC == 1 ? 3 : 4)) void linear_glds_kernel(vcr_linear_args p, int tiles_m, int tiles_n) {
+__global__ __launch_bounds__(256, (BK == 32 ? LINEAR_WG_PER_CU_BK32 : LINEAR_BLOCKED_ACC == 1 ? 3 : LINEAR_WG_PER_CU_BK16)) void linear_glds_kernel(vcr_linear_args p, int tiles_m, int tiles_n) {
   linear_glds_body<BK, MS, BMV>(p, tiles_m, tiles_n, (int)blockIdx.x);
 }
 // Two independent linears of the same kernel configuration as ONE launch (the first n0 workgroups work on p0, the rest
 // on p1): the encoder's and the decoder's output projections, or enc.ffn1 beside dec.cross.q -- fewer, fuller rounds of
 // workgroups; each tile is computed exactly as in its own launch.
 template <int BK, int MS, int BMV>
-__global__ __launch_bounds__(256, (BK == 32 ? 2 : LINEAR_BLOCKED_ACC == 1 ? 3 : 4)) void linear_glds_pair_kernel(vcr_linear_args p0, vcr_linear_args p1, int tm0,
+__global__ __launch_bounds__(256, (BK == 32 ? LINEAR_WG_PER_CU_BK32 : LINEAR_BLOCKED_ACC == 1 ? 3 : LINEAR_WG_PER_CU_BK16)) void linear_glds_pair_kernel(vcr_linear_args p0, vcr_linear_args p1, int tm0,
                                                                                  int tn0, int tm1, int tn1) {
   const int n0 = tm0 * tn0;
   if ((int)blockIdx.x < n0) linear_glds_body<BK, MS, BMV>(p0, tm0, tn0, (int)blockIdx.x);
@@ -543,22 +545,34 @@ __global__ __launch_bounds__(256, (BK == 32 ? 2 : LINEAR_BLOCKED_ACC == 1 ? 3 : 
 
 }  // namespace
 
+// ---- host side: validate the call, decode what its variant forces, choose the launch (linear_plan), launch it ----
 namespace {
-struct LinearPlan { bool glds, bk16, ms16, bm_free, small_free, ln_in, st_out; int bm, tiles_m, tiles_n, vec, lds; long t96, t128; };
+// One launch, completely: the kernel family (LDS-DMA, or the register-staged fallback: 128 rows, BK 32, 32x32x2), k-slab, MFMA
+// shape (16 = 16x16x4, 32 = 32x32x2), tile rows, the grid, the epilogue's 16-B flag and the dynamic LDS bytes.
+struct LinearPlan { bool glds; int bk, ms, bm, tiles_m, tiles_n, vec, lds; };
+// Forced by vcr_linear_args.variant: k-slab, MFMA shape, tile rows (0 = free); any: something, the staging included;
+// rows_free: neither the tile rows nor the 32x32x2 shape (bit 10 counts even where bit 4 overrules it).
+struct LinearForced { int bk, ms, rows; bool any, rows_free; };
+// One linear of a launch of one or two: its arguments, what follows from their pointers and pitches (16 B per lane in the
+// epilogue; whether the LDS-DMA family can take it) and what its variant forces.
+struct LinearHalf { const vcr_linear_args* a; int vec; bool glds; LinearForced v; };
 
-// Launches of less than one round (t128 < 2 x CUs): tile height in {128, 96, 64, 32} minimising g(ceil(tiles / CUs)) x
+constexpr int LINEAR_SMALL_M = 16384;                    // fewer rows = a small problem: up to 7 pairs of 1024 points per call
+constexpr double LINEAR_ROWS96_MARGIN = 1.02;            // 96-row tiles when the cost model prefers them by more than 2 %
+constexpr int LINEAR_ROWS[4] = {128, 96, 64, 32};        // the tile heights
+
+// Launches of less than one round (t128 < 2 x CUs; any other: 0): tile height in {128, 96, 64, 32} minimising g(ceil(tiles / CUs)) x
 // (rows + 24) -- workgroups spread one per CU first; a workgroup costs its rows plus a fixed prologue / epilogue /
 // pipeline-fill share (~24 rows' worth); two co-resident ones take 1.75 x one (profiles/rounds1-3/r3z_sweep_bm.txt), a third
 // waits for a slot.  tiles_by_h: the launch's (or the pair's) tile counts at the four heights.
-int small_grid_rows(const long* tiles_by_h) {
-  static const int hs[4] = {128, 96, 64, 32};
+int small_grid_rows(const long* tiles_by_h, int cus) {
+  if (tiles_by_h[0] >= (long)LINEAR_WG_PER_CU_BK32 * cus) return 0;
   int best = 128;
   double bc = 1e30;
-  const int cus = vcr_cu_count();
   for (int i = 0; i < 4; ++i) {
     const long per_cu = (tiles_by_h[i] + cus - 1) / cus;
-    const double c = ((double)(per_cu / 2) * 1.75 + (double)(per_cu & 1)) * (hs[i] + 24);
-    if (c < bc - 1e-9) { bc = c; best = hs[i]; }
+    const double c = ((double)(per_cu / 2) * 1.75 + (double)(per_cu & 1)) * (LINEAR_ROWS[i] + 24);
+    if (c < bc - 1e-9) { bc = c; best = LINEAR_ROWS[i]; }
   }
   return best;
 }
@@ -578,205 +592,217 @@ double launch_cost(long tiles, int slots, int rows) {
   return c * rows;
 }
 
-// validation + kernel choice of one linear (shared by vcr_linear_f32 and vcr_linear_pair_f32)
-// (bm_override: 0 = decide here, else the tile rows a paired launch decided for both of its halves; 64 / 32 also mean the
-//  small-grid configuration BK 32 + 16x16x4)
-int linear_plan(const vcr_linear_args* a, LinearPlan* pl, int bm_override = 0, bool in_pair = false) {
+// validation of one linear (the order of the checks decides which of two applicable codes a call gets)
+int linear_check(const vcr_linear_args* a, LinearHalf* f) {
   if (!a || !a->x || !a->w || (!a->y && !a->segmax_out)) return VCR_EINVAL;
   if (a->segmax_out && (a->seg_k <= 0 || !a->relu || a->residual || a->ln_stats_in || a->stats_out || (a->ld_segmax & 3) ||
-                        a->ld_segmax < a->N || ((uintptr_t)a->segmax_out & 15) || (a->variant & 4)))
+                        a->ld_segmax < a->N || ((uintptr_t)a->segmax_out & 15) || (a->variant & VCR_LINEAR_REGSTAGE)))
     return VCR_EINVAL;
   if (a->M <= 0 || a->N <= 0 || a->K <= 0 || (a->K % 32) != 0) return VCR_EINVAL;
   const int variant = a->variant;                    // tuning / test selector carried by the call (see vcr_hip.h)
-  if (variant & ~(4 | 8 | 16 | 64 | 1024 | 2048 | 4096 | 8192 | 16384)) return VCR_EINVAL;   // retired selectors (1, 32, 128, 256, 512) are refused, not ignored
-  if ((variant & 2048) && (variant & (4096 | 1024 | 4))) return VCR_EINVAL;    // 96-row tiles exist on the LDS-DMA 16x16x4 kernels only
-  if ((variant & (8192 | 16384)) && ((variant & (4096 | 2048 | 1024 | 64 | 4)) || (variant & (8192 | 16384)) == (8192 | 16384)))
+  constexpr int ROWS64_32 = VCR_LINEAR_ROWS64 | VCR_LINEAR_ROWS32;
+  if (variant & ~(VCR_LINEAR_REGSTAGE | VCR_LINEAR_BK32 | VCR_LINEAR_MFMA16 | VCR_LINEAR_BK16 | VCR_LINEAR_MFMA32 | VCR_LINEAR_ROWS96 |
+                  VCR_LINEAR_ROWS128 | ROWS64_32))
+    return VCR_EINVAL;                                   // retired selectors (1, 32, 128, 256, 512) are refused, not ignored
+  if ((variant & VCR_LINEAR_ROWS96) && (variant & (VCR_LINEAR_ROWS128 | VCR_LINEAR_MFMA32 | VCR_LINEAR_REGSTAGE)))
+    return VCR_EINVAL;                                   // 96-row tiles exist on the LDS-DMA 16x16x4 kernels only
+  if ((variant & ROWS64_32) && ((variant & (VCR_LINEAR_ROWS128 | VCR_LINEAR_ROWS96 | VCR_LINEAR_MFMA32 | VCR_LINEAR_BK16 | VCR_LINEAR_REGSTAGE)) ||
+                                (variant & ROWS64_32) == ROWS64_32))
     return VCR_EINVAL;                                   // 64- / 32-row tiles: LDS-DMA, BK 32, 16x16x4 only
   if ((a->ldx & 3) || a->ldx < a->K || (a->y && a->ldy < a->N) || (a->residual && a->ldr < a->N)) return VCR_EINVAL;
   if (((uintptr_t)a->x | (uintptr_t)a->w) & 15) return VCR_EINVAL;
-  pl->tiles_n = (a->N + BN - 1) / BN;
-  pl->vec = (a->N % 4 == 0) && (!a->y || ((a->ldy % 4 == 0) && (((uintptr_t)a->y & 15) == 0))) &&
-            (!a->bias || ((uintptr_t)a->bias & 15) == 0) &&
-            (!a->residual || ((a->ldr % 4 == 0) && ((uintptr_t)a->residual & 15) == 0));
+  f->a = a;
+  f->vec = (a->N % 4 == 0) && (!a->y || ((a->ldy % 4 == 0) && (((uintptr_t)a->y & 15) == 0))) &&
+           (!a->bias || ((uintptr_t)a->bias & 15) == 0) &&
+           (!a->residual || ((a->ldr % 4 == 0) && ((uintptr_t)a->residual & 15) == 0));
   if (a->ln_stats_in || a->stats_out) {                  // fused LayerNorm prologue / statistics epilogue
     if (a->ln_stats_in && (!a->ln_colsum || !a->bias || a->ln_nseg <= 0 || a->K < 2 || (a->K % a->ln_nseg))) return VCR_EINVAL;
     if (a->stats_out && (a->N % 64)) return VCR_EINVAL;
-    if (!pl->vec || (variant & 4)) return VCR_EUNSUPPORTED;   // the LDS-DMA kernels move 16 B per lane
+    if (!f->vec || (variant & VCR_LINEAR_REGSTAGE)) return VCR_EUNSUPPORTED;   // the LDS-DMA kernels move 16 B per lane
     if (a->ln_stats_in && ((uintptr_t)a->ln_colsum & 15)) return VCR_EINVAL;
   }
-  if (a->segmax_out && !pl->vec) return VCR_EUNSUPPORTED;
-  pl->glds = !(variant & 4) && pl->vec;                  // LDS-DMA staging, one tile per workgroup
-  pl->ln_in = a->ln_stats_in != nullptr; pl->st_out = a->stats_out != nullptr;
-  // Without a residual: BK = 16, four workgroups per CU (measured +2-3 % on the qkv / ffn1 / kv projections).
-  // With one: BK = 32 and the residual tile prefetched across the GEMM loop (bit 3 forces BK 32, bit 6 BK 16).
-  // MFMA shape: bit 4 (16) forces 16x16x4, bit 10 (1024) forces 32x32x2.  Automatic: 16x16x4 for the launches with a
-  // residual (the BK 32 kernels: measured in the pipeline at BASELINE configs[1], wo 155 -> 151 us, ffn2 276 -> 266 us),
-  // 32x32x2 for the BK 16 kernels (qkv / ffn1 / kv / q / conv3: equal within 1 %); DESIGN.md 5.1.
-  // ... except a launch of its own whose grid is at most ONE round of the BK 16 kernel's 1024 slots (conv3 at BASELINE
-  // configs[1]: 1024 tiles): every workgroup then stores its tile at the same time with no k loop left to run under the
-  // stores; two rounds of the BK 32 kernel's 512 slots drift apart instead.  Measured inside the forward on one box
-  // (profiles/rounds1-3/r3r_ab_conv3_bk32.txt): conv3 0.148 -> 0.1425 ms.  K >= 512 only (sn1_pq, K = 128: 0.047 -> 0.049 with BK 32).
-  const bool one_round16 = !in_pair && variant == 0 && a->M >= 16384 && a->K >= 512 &&
-                           (long)((a->M + 127) / 128) * pl->tiles_n <= 4L * vcr_cu_count();
-  pl->bk16 = ((!a->residual && !one_round16) || (variant & 64)) && !(variant & 8);
-  pl->ms16 = (variant & 16) ? true : (variant & 1024) ? false : (LINEAR_MS_DEFAULT == 16 || (LINEAR_MS_DEFAULT == 0 && !pl->bk16));
-  // Tile rows: bit 11 (2048) forces 96, bit 12 (4096) forces 128.  Automatic: 96 when the launch cost model above
-  // prefers it by > 2 %, on the BK 32 kernels only (two workgroups per CU; measured at BASELINE configs[2], M = 36 864:
-  // ffn2 0.335 -> 0.309 ms, cross.wo 0.184 -> 0.170, the wo pair 0.357 -> 0.340.  The BK 16 kernels run four
-  // workgroups per CU, their last round costs little, and 96-row tiles measured 0-6 % SLOWER there).
-  const int slots = vcr_cu_count() * (pl->bk16 ? 4 : 2); // CUs (MI355X: 256) x resident workgroups per CU
-  const long t128 = (long)((a->M + 127) / 128) * pl->tiles_n, t96 = (long)((a->M + 95) / 96) * pl->tiles_n;
-  pl->t96 = t96; pl->t128 = t128;
-  pl->bm_free = pl->glds && !(variant & (4096 | 2048 | 1024 | 8192 | 16384));   // nothing forces the tile rows or the 32x32x2 shape
-  // Small problems (M < 16 384 rows: up to 7 pairs of 1024 points per call), nothing forced (tests and benchmarks that
-  // pin BK / the MFMA shape keep what they ask for): ALWAYS the 16x16x4 shape, so that the results of a launch do not
-  // depend on which tile height its grid makes it take (all heights are bit-identical on that shape) -- the merged and
-  // the separate projections of one forward, for example, give the same bits at any size.
-  pl->small_free = pl->glds && variant == 0 && a->M < 16384;
-  if (pl->small_free) pl->ms16 = true;
-  bool bm96 = pl->glds && !(variant & (4096 | 1024 | 8192 | 16384)) &&
-              ((variant & 2048) || (!pl->bk16 && 1.02 * launch_cost(t96, slots, 96) < launch_cost(t128, slots, 128)));
-  if ((variant & 2048) && !bm96) return VCR_EUNSUPPORTED;
-  int bm = bm96 ? 96 : BM;
-  if (variant & (8192 | 16384)) {
-    if (!pl->glds) return VCR_EUNSUPPORTED;
-    bm = (variant & 8192) ? 64 : 32;
-  } else if (bm_override && pl->bm_free && (bm_override >= 96 || pl->small_free)) {
-    bm = bm_override;
-  } else if (!bm_override && pl->small_free && t128 < 2L * vcr_cu_count()) {
-    const long th[4] = {t128, t96, (long)((a->M + 63) / 64) * pl->tiles_n, (long)((a->M + 31) / 32) * pl->tiles_n};
-    bm = small_grid_rows(th);
-    if (bm >= 96) bm = bm96 ? 96 : 128;                  // (>= 96 rows: the regular choice above, with its k-slab and shape)
+  if (a->segmax_out && !f->vec) return VCR_EUNSUPPORTED;
+  f->glds = !(variant & VCR_LINEAR_REGSTAGE) && f->vec;  // LDS-DMA staging, one tile per workgroup
+  if ((variant & (VCR_LINEAR_ROWS96 | ROWS64_32)) && !f->glds) return VCR_EUNSUPPORTED;   // (the fallback has 128-row tiles only)
+  return VCR_OK;
+}
+
+// bit 3 forces BK 32 (over bit 6: BK 16), bit 4 the 16x16x4 shape (over bit 10: 32x32x2), bits 11 - 14 the tile rows
+LinearForced linear_forced(int variant) {
+  return {(variant & VCR_LINEAR_BK32) ? 32 : (variant & VCR_LINEAR_BK16) ? 16 : 0,
+          (variant & VCR_LINEAR_MFMA16) ? 16 : (variant & VCR_LINEAR_MFMA32) ? 32 : 0,
+          (variant & VCR_LINEAR_ROWS96) ? 96 : (variant & VCR_LINEAR_ROWS128) ? 128 : (variant & VCR_LINEAR_ROWS64) ? 64 :
+          (variant & VCR_LINEAR_ROWS32) ? 32 : 0,
+          variant != 0, !(variant & (VCR_LINEAR_ROWS96 | VCR_LINEAR_ROWS128 | VCR_LINEAR_ROWS64 | VCR_LINEAR_ROWS32 | VCR_LINEAR_MFMA32))};
+}
+
+// The choice: the plans of a launch of n = 1 (vcr_linear_f32) or 2 (vcr_linear_pair_f32) validated linears; returns whether it
+// is ONE launch -- two halves are when they resolve to the same LDS-DMA kernel configuration (k-slab, MFMA shape, tile rows;
+// neither with a fused max); when they do not, pl[] holds what each half takes as a launch of its own.
+bool linear_plan(const LinearHalf* h, int n, LinearPlan* pl) {
+  const int cus = vcr_cu_count();                        // MI355X: 256
+  // Tile rows of the regular configuration: 96 when the launch cost model above prefers them by > 2 %, on the BK 32 kernels
+  // only (two workgroups per CU; measured at BASELINE configs[2], M = 36 864: ffn2 0.335 -> 0.309 ms, cross.wo 0.184 ->
+  // 0.170, the wo pair 0.357 -> 0.340.  The BK 16 kernels run four workgroups per CU, their last round costs little, and
+  // 96-row tiles measured 0-6 % SLOWER there).  t: the grid's tile counts at the four heights.
+  auto regular_rows = [&](bool bk32, const long* t) {
+    const int slots = cus * (bk32 ? LINEAR_WG_PER_CU_BK32 : LINEAR_WG_PER_CU_BK16);   // CUs x resident workgroups per CU
+    return bk32 && LINEAR_ROWS96_MARGIN * launch_cost(t[1], slots, 96) < launch_cost(t[0], slots, 128) ? 96 : 128;
+  };
+  long total[4] = {0, 0, 0, 0};                          // the launch's tile counts at the four heights
+  int bk[2], ms[2], rows[2];
+  bool small_free[2], rows_free[2];
+  for (int i = 0; i < n; ++i) {
+    const vcr_linear_args& a = *h[i].a;
+    const LinearForced& v = h[i].v;
+    const int tiles_n = (a.N + BN - 1) / BN;
+    long t[4];
+    for (int j = 0; j < 4; ++j) { t[j] = (long)((a.M + LINEAR_ROWS[j] - 1) / LINEAR_ROWS[j]) * tiles_n; total[j] += t[j]; }
+    // Without a residual: BK = 16, four workgroups per CU (measured +2-3 % on the qkv / ffn1 / kv projections).
+    // With one: BK = 32 and the residual tile prefetched across the GEMM loop (bit 3 forces BK 32, bit 6 BK 16).
+    // ... except a launch of its own whose grid is at most ONE round of the BK 16 kernel's 1024 slots (conv3 at BASELINE
+    // configs[1]: 1024 tiles): every workgroup then stores its tile at the same time with no k loop left to run under the
+    // stores; two rounds of the BK 32 kernel's 512 slots drift apart instead.  Measured inside the forward on one box
+    // (profiles/rounds1-3/r3r_ab_conv3_bk32.txt): conv3 0.148 -> 0.1425 ms.  K >= 512 only (sn1_pq, K = 128: 0.047 -> 0.049 with BK 32).
+    const bool one_round16 = n == 1 && !v.any && a.M >= LINEAR_SMALL_M && a.K >= 512 && t[0] <= (long)LINEAR_WG_PER_CU_BK16 * cus;
+    bk[i] = v.bk ? v.bk : (a.residual || one_round16) ? 32 : 16;
+    // Small problems, nothing forced (tests and benchmarks that pin BK / the MFMA shape keep what they ask for): ALWAYS the
+    // 16x16x4 shape, so that the results of a launch do not depend on which tile height its grid makes it take (all heights
+    // are bit-identical on that shape) -- the merged and the separate projections of one forward, for example, give the
+    // same bits at any size.
+    small_free[i] = h[i].glds && !v.any && a.M < LINEAR_SMALL_M;
+    // MFMA shape otherwise: 16x16x4 for the launches with a residual (the BK 32 kernels: measured in the pipeline at BASELINE
+    // configs[1], wo 155 -> 151 us, ffn2 276 -> 266 us), 32x32x2 for the BK 16 kernels (qkv / ffn1 / kv / q / conv3: equal
+    // within 1 %); DESIGN.md 5.1.
+    ms[i] = v.ms ? v.ms : small_free[i] ? 16 : LINEAR_MS_DEFAULT ? LINEAR_MS_DEFAULT : bk[i] == 32 ? 16 : 32;
+    rows_free[i] = h[i].glds && v.rows_free;
+    rows[i] = v.rows ? v.rows : rows_free[i] ? regular_rows(bk[i] == 32, t) : BM;
+    const int sr = small_free[i] ? small_grid_rows(t, cus) : 0;
+    if (sr && sr < 96) rows[i] = sr;                     // (>= 96 rows: the regular choice, with its k-slab and shape)
   }
-  if (bm < 96) pl->bk16 = false;                         // 64 / 32 rows: the small-grid configuration
-  if (bm < 128) pl->ms16 = true;
-  pl->bm = bm;
-  pl->tiles_m = (a->M + bm - 1) / bm;
+  if (n == 2) {                                          // tile rows from the COMBINED grid (the two halves share the rounds)
+    int joint = small_free[0] && small_free[1] ? small_grid_rows(total, cus) : 0;     // a small grid even together
+    if (joint >= 96 || (joint == 0 && rows_free[0] && rows_free[1])) {
+      const bool r = h[0].a->residual != nullptr, rb = h[1].a->residual != nullptr;   // (the regular k-slab: BK 32 iff a residual)
+      joint = r == rb ? regular_rows(r, total) : 0;
+    }
+    if (joint) rows[0] = rows[1] = joint;
+  }
   static_assert(2 * sizeof(TileGT<16>) == 2 * (BM + BN) * 16 * 4 && 2 * sizeof(TileGT<32, 96>) == 2 * (96 + BN) * 32 * 4, "stage size below");
-  const int bkv = pl->bk16 ? 16 : 32;
-  const int stage = 2 * (bm + BN) * bkv * 4 > 4 * 32 * 68 * 4 ? 2 * (bm + BN) * bkv * 4 : 4 * 32 * 68 * 4;   // 2 x TileGT<BK, BMV> or the epilogue slices
-  pl->lds = stage + (pl->ln_in ? bm * 2 * 4 : 0);
+  for (int i = 0; i < n; ++i) {
+    const vcr_linear_args& a = *h[i].a;
+    const bool glds = h[i].glds;                       // else the alignment-free fallback: register staging, one configuration
+    const int bm = rows[i];
+    if (!glds || bm < 96) bk[i] = 32;                    // 64 / 32 rows: the small-grid configuration
+    ms[i] = !glds ? 32 : bm < 128 ? 16 : ms[i];
+    const int stage = 2 * (bm + BN) * bk[i] * 4, epi = 4 * 32 * 68 * 4;   // 2 x TileGT<BK, BMV> or the epilogue slices
+    pl[i] = LinearPlan{glds, bk[i], ms[i], bm, (a.M + bm - 1) / bm, (a.N + BN - 1) / BN, h[i].vec,
+                       glds ? (stage > epi ? stage : epi) + (a.ln_stats_in ? bm * 2 * 4 : 0) : (int)(2 * sizeof(TileT<32>))};
+  }
+  if (n == 1) return true;
+  if (pl[0].glds && pl[1].glds && pl[0].bk == pl[1].bk && pl[0].ms == pl[1].ms && pl[0].bm == pl[1].bm && !h[0].a->segmax_out &&
+      !h[1].a->segmax_out) {                             // (LayerNorm-in / statistics-out may differ: run-time flags of each half)
+    pl[0].lds = pl[1].lds = pl[0].lds > pl[1].lds ? pl[0].lds : pl[1].lds;
+    return true;
+  }
+  linear_plan(h, 1, pl);
+  linear_plan(h + 1, 1, pl + 1);
+  return false;
+}
+
+// validation, forced choices and plans of a call of n = 1 or 2 linears; the first error of a, then of b
+int linear_prepare(const vcr_linear_args* a, const vcr_linear_args* b, int n, LinearPlan* pl, bool* one_launch) {
+  const vcr_linear_args* args[2] = {a, b};
+  LinearHalf h[2];
+  for (int i = 0; i < n; ++i) {
+    const int rc = linear_check(args[i], &h[i]);
+    if (rc != VCR_OK) return rc;
+    h[i].v = linear_forced(args[i]->variant);
+  }
+  *one_launch = linear_plan(h, n, pl);
   return VCR_OK;
 }
 
 // dispatch over the template grid (BK, MS, BMV): F is a generic lambda taking three integral_constants
 template <class F>
 void linear_dispatch(const LinearPlan& pl, F&& f) {
-  using I16 = std::integral_constant<int, 16>;
-  using I32 = std::integral_constant<int, 32>;
-  using I96 = std::integral_constant<int, 96>;
-  using I128 = std::integral_constant<int, 128>;
-  using I64 = std::integral_constant<int, 64>;
+  using I16 = std::integral_constant<int, 16>; using I32 = std::integral_constant<int, 32>; using I64 = std::integral_constant<int, 64>;
+  using I96 = std::integral_constant<int, 96>; using I128 = std::integral_constant<int, 128>;
+  const bool bk16 = pl.bk == 16, ms16 = pl.ms == 16;
   if (pl.bm == 64) f(I32{}, I16{}, I64{});
   else if (pl.bm == 32) f(I32{}, I16{}, I32{});
-  else if (pl.bm == 96) { if (pl.bk16) f(I16{}, I16{}, I96{}); else f(I32{}, I16{}, I96{}); }
-  else if (pl.bk16) { if (pl.ms16) f(I16{}, I16{}, I128{}); else f(I16{}, I32{}, I128{}); }
-  else { if (pl.ms16) f(I32{}, I16{}, I128{}); else f(I32{}, I32{}, I128{}); }
+  else if (pl.bm == 96) { if (bk16) f(I16{}, I16{}, I96{}); else f(I32{}, I16{}, I96{}); }
+  else if (bk16) { if (ms16) f(I16{}, I16{}, I128{}); else f(I16{}, I32{}, I128{}); }
+  else { if (ms16) f(I32{}, I16{}, I128{}); else f(I32{}, I32{}, I128{}); }
+}
+
+// one launch of plan p on a
+int linear_launch(const LinearPlan& p, const vcr_linear_args& a, hipStream_t s) {
+  const dim3 grid(p.tiles_m * p.tiles_n), block(256);
+  int rc = 0;
+  if (p.glds) linear_dispatch(p, [&](auto bk, auto ms, auto bm) {
+    rc = vcr_launch<linear_glds_kernel<decltype(bk)::value, decltype(ms)::value, decltype(bm)::value>>(grid, block, p.lds, s, a, p.tiles_m, p.tiles_n);
+  });
+  else rc = vcr_launch<linear_kernel<32>>(grid, block, p.lds, s, a, p.tiles_m, p.tiles_n, p.vec);
+  return rc;
+}
+// ONE launch of p on a and q on b side by side (linear_plan gave them the same kernel configuration and LDS bytes)
+int linear_launch(const LinearPlan& p, const vcr_linear_args& a, const LinearPlan& q, const vcr_linear_args& b, hipStream_t s) {
+  const dim3 grid(p.tiles_m * p.tiles_n + q.tiles_m * q.tiles_n), block(256);
+  int rc = 0;
+  linear_dispatch(p, [&](auto bk, auto ms, auto bm) {
+    rc = vcr_launch<linear_glds_pair_kernel<decltype(bk)::value, decltype(ms)::value, decltype(bm)::value>>(
+        grid, block, p.lds, s, a, b, p.tiles_m, p.tiles_n, q.tiles_m, q.tiles_n);
+  });
+  return rc;
 }
 }  // namespace
+
+// Host-only, library-internal (forward.hip, tests): linear_plan's return code for vcr_linear_f32 (b == NULL) or
+// vcr_linear_pair_f32 on these arguments, whether a pair is ONE launch, and per half the form of the launch that computes it:
+// {LDS-DMA family, tile rows, k-slab, MFMA shape (16 = 16x16x4, 32 = 32x32x2: the one choice its BITS depend on), tiles_m,
+// tiles_n (the half's grid is their product), dynamic LDS bytes, 16-B epilogue}.
+extern "C" int vcr_linear_forms_(const vcr_linear_args* a, const vcr_linear_args* b, int* one_launch, int* form_a, int* form_b) {
+  LinearPlan pl[2];
+  bool one;
+  const int n = b ? 2 : 1, rc = linear_prepare(a, b, n, pl, &one);
+  if (rc != VCR_OK) return rc;
+  if (one_launch) *one_launch = one;
+  int* const forms[2] = {form_a, form_b};
+  for (int i = 0; i < n; ++i)
+    if (forms[i]) {
+      const int f[8] = {pl[i].glds, pl[i].bm, pl[i].bk, pl[i].ms, pl[i].tiles_m, pl[i].tiles_n, pl[i].lds, pl[i].vec};
+      memcpy(forms[i], f, sizeof(f));
+    }
+  return VCR_OK;
+}
 
 // Host-only: the kernel configuration vcr_linear_f32 would launch for these arguments, nothing launched.  Returns
 // rows | k-slab << 8 | (16x16x4 ? 1 << 16 : 0) | (LDS-DMA ? 1 << 17 : 0), or a negative VCR_E* code.
 extern "C" int vcr_linear_config(const vcr_linear_args* a) {
-  LinearPlan pl{};
-  const int rc = linear_plan(a, &pl);
-  if (rc != VCR_OK) return rc;
-  if (!pl.glds) return 128 | (32 << 8);
-  return pl.bm | ((pl.bk16 ? 16 : 32) << 8) | (pl.ms16 ? 1 << 16 : 0) | (1 << 17);
+  int f[8];
+  const int rc = vcr_linear_forms_(a, nullptr, nullptr, f, nullptr);
+  return rc != VCR_OK ? rc : f[1] | (f[2] << 8) | (f[3] == 16 ? 1 << 16 : 0) | (f[0] ? 1 << 17 : 0);
 }
 
 extern "C" int vcr_linear_f32(const vcr_linear_args* a, vcr_stream_t stream) {
   vcr_stream_scope bound(stream);
-  LinearPlan pl{};
-  const int rc = linear_plan(a, &pl);
-  if (rc != VCR_OK) return rc;
-  if (pl.glds) {
-    linear_dispatch(pl, [&](auto bk, auto ms, auto bm) {
-      constexpr int BKV = decltype(bk)::value, MSV = decltype(ms)::value, BMV = decltype(bm)::value;
-      VCR_DYN_LDS((linear_glds_kernel<BKV, MSV, BMV>), pl.lds);
-      hipLaunchKernelGGL((linear_glds_kernel<BKV, MSV, BMV>), dim3(pl.tiles_m * pl.tiles_n), dim3(256), pl.lds,
-                         (hipStream_t)stream, *a, pl.tiles_m, pl.tiles_n);
-    });
-  } else {
-    // alignment-free fallback (odd N, unaligned y / bias / residual; bit 2 forces it): register staging, scalar epilogue
-    const int lds32 = 2 * sizeof(TileT<32>);
-    VCR_DYN_LDS(linear_kernel<32>, lds32);
-    hipLaunchKernelGGL(linear_kernel<32>, dim3(pl.tiles_m * pl.tiles_n), dim3(256), lds32, (hipStream_t)stream, *a, pl.tiles_m,
-                       pl.tiles_n, pl.vec);
-  }
-  return VCR_LAUNCH_RC();
+  LinearPlan pl;
+  bool one;
+  const int rc = linear_prepare(a, nullptr, 1, &pl, &one);
+  return rc != VCR_OK ? rc : linear_launch(pl, *a, (hipStream_t)stream);
 }
 
-// Two independent linears as one launch when they resolve to the same LDS-DMA kernel configuration (k-slab, MFMA shape,
-// tile rows; neither with a fused max); otherwise exactly the two vcr_linear_f32 calls.  Same results.
-// the planning half of vcr_linear_pair_f32: both plans as a paired launch would take them, and whether it IS one launch
-static int linear_pair_plan(const vcr_linear_args* a, const vcr_linear_args* b, LinearPlan& pa, LinearPlan& pb, bool& same) {
-  int rc = linear_plan(a, &pa, 0, true);
-  if (rc == VCR_OK) rc = linear_plan(b, &pb, 0, true);
-  if (rc != VCR_OK) return rc;
-  int joint = 0;                                         // tile rows from the COMBINED grid (the two halves share the rounds)
-  if (pa.small_free && pb.small_free && pa.t128 + pb.t128 < 2L * vcr_cu_count()) {     // a small grid even together
-    const long th[4] = {pa.t128 + pb.t128, pa.t96 + pb.t96,
-                        (long)((a->M + 63) / 64) * pa.tiles_n + (long)((b->M + 63) / 64) * pb.tiles_n,
-                        (long)((a->M + 31) / 32) * pa.tiles_n + (long)((b->M + 31) / 32) * pb.tiles_n};
-    joint = small_grid_rows(th);
-  }
-  if (joint >= 96 || (joint == 0 && pa.bm_free && pb.bm_free)) {
-    const bool r = a->residual != nullptr, rb = b->residual != nullptr;     // (the regular k-slab: BK 32 iff a residual)
-    joint = 0;
-    if (r == rb) {
-      const int slots = vcr_cu_count() * (r ? 2 : 4);
-      joint = r && 1.02 * launch_cost(pa.t96 + pb.t96, slots, 96) < launch_cost(pa.t128 + pb.t128, slots, 128) ? 96 : 128;
-    }
-  }
-  if (joint) {
-    linear_plan(a, &pa, joint, true);
-    linear_plan(b, &pb, joint, true);
-  }
-  same = pa.glds && pb.glds && pa.bk16 == pb.bk16 && pa.ms16 == pb.ms16 && pa.bm == pb.bm &&
-         !a->segmax_out && !b->segmax_out;             // (LayerNorm-in / statistics-out may differ: run-time flags of each half)
-  return VCR_OK;
-}
-
-// Host-only, library-internal (forward.hip): the MFMA shape -- 1 = 16x16x4, 0 = 32x32x2, the one choice of a linear's
-// configuration that its BITS depend on -- that vcr_linear_f32 (b == NULL) or vcr_linear_pair_f32 would compute these arguments
-// with.  The forward's src-only launches of a later vcrnetIter pass pin the shape of the full-row launch they stand for.
-extern "C" int vcr_linear_shapes_(const vcr_linear_args* a, const vcr_linear_args* b, int* shape_a, int* shape_b) {
-  LinearPlan pa{}, pb{};
-  if (!b) {
-    const int rc = linear_plan(a, &pa);
-    if (rc == VCR_OK && shape_a) *shape_a = pa.glds ? (pa.ms16 ? 1 : 0) : 0;
-    return rc;
-  }
-  bool same = false;
-  int rc = linear_pair_plan(a, b, pa, pb, same);
-  if (rc != VCR_OK) return rc;
-  if (!same) {                                           // two separate launches, each planned on its own
-    rc = linear_plan(a, &pa);
-    if (rc == VCR_OK) rc = linear_plan(b, &pb);
-    if (rc != VCR_OK) return rc;
-  }
-  if (shape_a) *shape_a = pa.glds ? (pa.ms16 ? 1 : 0) : 0;
-  if (shape_b) *shape_b = pb.glds ? (pb.ms16 ? 1 : 0) : 0;
-  return VCR_OK;
-}
-
+// Two independent linears as one launch when they resolve to the same LDS-DMA kernel configuration, otherwise the two
+// launches each takes on its own (the second only when the first went out).  Same results.
 extern "C" int vcr_linear_pair_f32(const vcr_linear_args* a, const vcr_linear_args* b, vcr_stream_t stream) {
   vcr_stream_scope bound(stream);
-  LinearPlan pa{}, pb{};
-  bool same = false;
-  int rc = linear_pair_plan(a, b, pa, pb, same);
+  LinearPlan pl[2];
+  bool one;
+  int rc = linear_prepare(a, b, 2, pl, &one);
   if (rc != VCR_OK) return rc;
-  if (pb.lds > pa.lds) pa.lds = pb.lds;
-  if (!same) {
-    rc = vcr_linear_f32(a, stream);
-    return rc ? rc : vcr_linear_f32(b, stream);
-  }
-  linear_dispatch(pa, [&](auto bk, auto ms, auto bm) {
-    constexpr int BKV = decltype(bk)::value, MSV = decltype(ms)::value, BMV = decltype(bm)::value;
-    VCR_DYN_LDS((linear_glds_pair_kernel<BKV, MSV, BMV>), pa.lds);
-    hipLaunchKernelGGL((linear_glds_pair_kernel<BKV, MSV, BMV>), dim3(pa.tiles_m * pa.tiles_n + pb.tiles_m * pb.tiles_n),
-                       dim3(256), pa.lds, (hipStream_t)stream, *a, *b, pa.tiles_m, pa.tiles_n, pb.tiles_m, pb.tiles_n);
-  });
-  return VCR_LAUNCH_RC();
+  hipStream_t s = (hipStream_t)stream;
+  if (one) return linear_launch(pl[0], *a, pl[1], *b, s);
+  rc = linear_launch(pl[0], *a, s);
+  return rc ? rc : linear_launch(pl[1], *b, s);
 }
