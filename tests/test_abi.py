@@ -372,6 +372,68 @@ def test_linear_pair_launch_form_of_the_quoted_shapes(lib):
         (1, (1, 64, 32, 16, 188), (1, 64, 32, 16, 98))
 
 
+def test_edgeconv_launch_form_of_the_quoted_shapes(lib):
+    """vcr_edgeconv_forms_ (host-only, library-internal): what edgeconv_check / edgeconv_plan make of the EdgeConv launches
+    DESIGN and the tests quote, on 256 CUs: (code, form, grid) with form 0 = padded, 1 = packed, 2 = the hand-scheduled packed
+    kernel, 3 = bf16x3."""
+    from vcrnet_amd import native
+    I = ctypes.POINTER(ctypes.c_int)
+    lib.vcr_edgeconv_forms_.argtypes, lib.vcr_edgeconv_forms_.restype = [ctypes.POINTER(native.EdgeconvArgs), ctypes.c_int, I, I], ctypes.c_int
+
+    def form(M, N, k, bf16x3=False, pq=0x10000, b2=0x40000, x2=0x60000, ldx2=128):
+        a = native.EdgeconvArgs(pq, 256, 0x20000, k, M, N, 0x30000, b2, 0x50000, 128, x2, ldx2)   # (never dereferenced on the host)
+        f, g = ctypes.c_int(-1), ctypes.c_int(-1)
+        return lib.vcr_edgeconv_forms_(ctypes.byref(a), int(bf16x3), ctypes.byref(f), ctypes.byref(g)), f.value, g.value
+    PADDED, PACKED, PIPE, BF16X3 = 0, 1, 2, 3
+    assert form(32768, 1024, 20) == (0, PIPE, 512)           # configs[1]: 4096 groups on 2 x 256 slots
+    assert form(8192, 4096, 40) == (0, PIPE, 512)            # configs[4]: 2048 groups
+    assert form(74, 37, 20) == (0, PIPE, 10) and form(74, 37, 40) == (0, PIPE, 19)      # fewer groups than slots: one each
+    assert form(74, 37, 20, x2=0x60004) == (0, PACKED, 10) and form(74, 37, 20, ldx2=130) == (0, PACKED, 10)
+    assert form(74, 37, 20, b2=0x40004) == (0, PACKED, 10)
+    assert form(192, 96, 7) == (0, PADDED, 192) and form(140, 70, 33) == (0, PADDED, 140)   # min(M, 2048)
+    assert form(4096, 1024, 7) == (0, PADDED, 2048) and form(4096, 1024, 33) == (0, PADDED, 2048)
+    assert form(4096, 1024, 65) == (-1, -1, -1)
+    assert form(32768, 1024, 20, bf16x3=True) == (0, BF16X3, 1024) and form(600, 300, 20, bf16x3=True) == (0, BF16X3, 75)
+    assert form(406, 203, 7, bf16x3=True) == (-3, -1, -1)    # no static row -> point map: VCR_EUNSUPPORTED
+    assert form(600, 300, 20, bf16x3=True, pq=0x10004) == (-1, -1, -1)
+    assert lib.vcr_edgeconv_forms_(None, 0, None, None) == -1
+
+
+def test_gathermax_launch_form_of_the_quoted_shapes(lib):
+    """vcr_gathermax_forms_ (host-only, library-internal): what gathermax_check / gathermax_plan make of the shapes of
+    test_gathermax_lds_and_l2_paths_are_exact and of the limits DESIGN quotes: (code, form, channel slice, grid, LDS bytes)
+    with form 0 = gathers through L2 (one wave per point), 1 = out of LDS (one workgroup per cloud and slice, N x (slice + 4)
+    floats)."""
+    from vcrnet_amd import native
+    I = ctypes.POINTER(ctypes.c_int)
+    lib.vcr_gathermax_forms_.argtypes, lib.vcr_gathermax_forms_.restype = [ctypes.POINTER(native.GathermaxArgs), I, I, I, I], ctypes.c_int
+
+    def form(B, N, k=20, C=256, variant=0, idx=0x20000):
+        a = native.GathermaxArgs(0x10000, 2 * C, C, idx, k, B * N, N, 0x30000, C, variant, None)
+        o = [ctypes.c_int(-1) for _ in range(4)]
+        return (lib.vcr_gathermax_forms_(ctypes.byref(a), *[ctypes.byref(x) for x in o]),) + tuple(x.value for x in o)
+    L2, LDS, REFUSED, INVALID = 0, 1, (-3, -1, -1, -1, -1), (-1, -1, -1, -1, -1)
+    assert form(32, 1024) == (0, LDS, 32, 256, 147456) and form(48, 768) == (0, LDS, 32, 384, 110592)
+    assert form(24, 1000, k=40) == (0, LDS, 32, 192, 144000)          # 192 workgroups exactly
+    assert form(32, 1066) == (0, LDS, 32, 256, 153504)                # the last N whose 32-channel slice fits 150 KB
+    assert form(32, 1067) == (0, LDS, 16, 512, 85360)
+    assert form(4, 1024) == (0, L2, 0, 1024, 0)                       # 32 workgroups: the L2 gathers, four points each
+    assert form(64, 333, C=96) == (0, LDS, 32, 192, 47952) and form(200, 64, C=32) == (0, LDS, 32, 200, 9216)
+    assert form(32, 2048) == (0, LDS, 16, 512, 163840)                # the last N whose 16-channel slice fits a CU's 160 KB
+    assert form(32, 2049) == (0, L2, 0, 16392, 0)
+    # forced forms: any grid size; refused when the slice of one cloud does not fit, unknown values are argument errors
+    assert form(32, 1024, variant=32) == (0, LDS, 32, 256, 147456) and form(4, 1024, variant=32) == (0, LDS, 32, 32, 147456)
+    assert form(32, 1067, variant=32) == (0, LDS, 32, 256, 153648) and form(32, 2049, variant=32) == REFUSED
+    assert form(32, 1024, variant=16) == (0, LDS, 16, 512, 81920) and form(32, 2049, variant=16) == REFUSED
+    assert form(32, 1024, variant=8) == (0, LDS, 8, 1024, 49152) and form(32, 2049, variant=8) == (0, LDS, 8, 1024, 98352)
+    assert form(32, 1024, variant=1) == (0, L2, 0, 8192, 0) and form(32, 2049, variant=1) == (0, L2, 0, 16392, 0)
+    assert form(32, 1024, variant=5) == INVALID and form(4, 1024, variant=5) == INVALID
+    # the LDS form's 16-B index loads need an aligned list, and a k of 20 / 40
+    assert form(32, 1024, idx=0x20004) == (0, L2, 0, 8192, 0) and form(32, 1024, idx=0x20004, variant=32) == REFUSED
+    assert form(32, 1024, k=7) == (0, L2, 0, 8192, 0) and form(32, 1024, k=7, variant=16) == REFUSED
+    assert lib.vcr_gathermax_forms_(None, None, None, None, None) == -1
+
+
 def test_module_contract_on_cpu():
     """Constructor / state-dict contract of the reference module without a GPU."""
     from types import SimpleNamespace

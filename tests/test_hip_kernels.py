@@ -519,6 +519,72 @@ def test_edgeconv_bf16x3(nat, B, N, k):
     assert e3 <= 4e-6 * math.sqrt(128) + 1e-6 and e32 <= 4e-6 * math.sqrt(128) + 1e-6
 
 
+def _edgeconv_inputs(B, N, k):
+    g = torch.Generator().manual_seed(B * N + k)
+    M = B * N
+    pq = dev(torch.randn(M, 256, generator=g))
+    idx = dev(torch.randint(0, N, (M, k), generator=g).int())
+    w2 = dev(torch.randn(128, 128, generator=g) / math.sqrt(128))
+    b2 = dev(torch.randn(128, generator=g) * 0.3)
+    return pq, idx, w2, b2
+
+
+def _edgeconv_form(nat, pq, idx, N, w2, b2, x1, x2):
+    """(code, form, grid) of vcr_edgeconv_f32 for these very pointers: form 0 padded, 1 packed, 2 hand-scheduled packed."""
+    import ctypes
+    a = nat.EdgeconvArgs(nat.ptr(pq), pq.stride(0), nat.ptr(idx), idx.shape[-1], pq.shape[0], N, nat.ptr(w2), nat.ptr(b2),
+                         nat.ptr(x1), x1.stride(0), nat.ptr(x2), x2.stride(0))
+    fn = nat.lib().vcr_edgeconv_forms_
+    fn.argtypes = [ctypes.POINTER(nat.EdgeconvArgs), ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    form, grid = ctypes.c_int(-1), ctypes.c_int(-1)
+    return fn(ctypes.byref(a), 0, ctypes.byref(form), ctypes.byref(grid)), form.value, grid.value
+
+
+@pytest.mark.parametrize("k,misaligned", [(20, "x2"), (40, "x2"), (20, "b2")])
+def test_edgeconv_packed_kernel_serves_unaligned_rows(nat, k, misaligned):
+    """edgeconv_dg_packed_kernel -- what vcr_edgeconv_f32 launches when x2 / b2 are not 16-B aligned or ldx2 % 4 != 0 (the
+    hand-scheduled kernel stores x2 as 16-B pieces) -- gives the bits of the aligned call: same MFMA order per output, and a
+    max is exact.  74 points are ragged against both group sizes (8 and 4) and leave workgroups of the launch without a
+    group; the columns beside a pitched x2 stay untouched."""
+    B, N = 2, 37
+    M = B * N
+    pq, idx, w2, b2 = _edgeconv_inputs(B, N, k)
+    x1, x2 = nat.edgeconv(pq, idx, N, w2, b2)
+    assert _edgeconv_form(nat, pq, idx, N, w2, b2, x1, x2)[:2] == (0, 2)
+    y1 = torch.empty(M, 128, device="cuda")
+    if misaligned == "x2":
+        big = torch.full((M, 130), -7.0, device="cuda")
+        y2, b2m = big[:, 1:129], b2                              # 4 B off, pitch 130
+    else:
+        buf = torch.empty(129, device="cuda")
+        buf[1:] = b2
+        y2, b2m = torch.empty(M, 128, device="cuda"), buf[1:]    # only the bias 4 B off
+    assert _edgeconv_form(nat, pq, idx, N, w2, b2m, y1, y2)[:2] == (0, 1)
+    nat.edgeconv(pq, idx, N, w2, b2m, out=(y1, y2))
+    assert torch.equal(y1, x1) and torch.equal(y2, x2)
+    if misaligned == "x2":
+        assert bool((big[:, 0] == -7.0).all()) and bool((big[:, 129] == -7.0).all())
+
+
+@pytest.mark.parametrize("k", [33, 64])
+def test_edgeconv_padded_kernel_with_two_row_tiles(nat, k):
+    """edgeconv_dg_kernel with 33 <= k <= 64: a point's edge rows fill two 32-row MFMA tiles (the second padded with the last
+    neighbour at k = 33, full at k = 64).  x1 = max_j relu(P[nbr_j] + Q) to the bit (one fp32 add, a max is exact); x2 against
+    the fp64 product of the fp32-rounded rows, within the family's tolerance (test_edgeconv_bf16x3)."""
+    B, N = 2, 70
+    M = B * N
+    pq, idx, w2, b2 = _edgeconv_inputs(B, N, k)
+    x1, x2 = nat.edgeconv(pq, idx, N, w2, b2)
+    assert _edgeconv_form(nat, pq, idx, N, w2, b2, x1, x2) == (0, 0, M)
+    nbr = idx.long() + (torch.arange(M, device="cuda") // N * N).view(-1, 1)
+    h = torch.relu(pq[:, :128][nbr] + pq[:, None, 128:])          # fp32, as the kernel rounds it
+    assert torch.equal(x1, h.max(1)[0])
+    ref = torch.relu((h.cpu().double() @ w2.cpu().double().t()).max(1)[0] + b2.cpu().double())
+    e32 = (x2.cpu().double() - ref).abs().max().item()
+    print(f"edgeconv padded B={B} N={N} k={k}: max|x2 - fp64| {e32:.2e}")
+    assert e32 <= 4e-6 * math.sqrt(128) + 1e-6
+
+
 @pytest.mark.parametrize("bf16x3", [False, True])
 @pytest.mark.parametrize("N,shift", [(256, 0), (192, 0), (1024, 2), (100, 1), (300, 0)])
 def test_sdpa(nat, N, shift, bf16x3):

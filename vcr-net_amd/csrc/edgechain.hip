@@ -18,7 +18,7 @@
 // channels, tile after tile, and folds them into per-point registers with static indexing; the point's value is
 // stored when its group's fifth tile has passed.  MFMA accumulators have the channel on the lane, so the stores are
 // 128-B rows.
-#include "common.h"
+#include "edge_group.h"
 
 namespace {
 
@@ -36,12 +36,14 @@ __device__ __forceinline__ void unroll_impl(F&& f, std::integer_sequence<int, I.
 template <int N, class F>
 __device__ __forceinline__ void unroll(F&& f) { unroll_impl<N>(f, std::make_integer_sequence<int, N>{}); }
 
-// fold one accumulator tile (rows = edges, lane = channel) into the per-point maxima of its group; TT = tile mod 5
+// fold one accumulator tile (rows = edges, lane = channel) into the per-point maxima of its group; TT = tile mod 5.
+// edge_group.h's edge_fold written out: as a loop over that helper the k = 20 kernel's selects and maxima come out in
+// another order (60 lines of its assembly), so this kernel keeps its own copy
 template <int KE, int TT, int G>
 __device__ __forceinline__ void fold_tile(const f32x16& v, int half, float lowest, float (&pm)[G]) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int e0 = 32 * TT + (r & 3) + 8 * (r >> 2), e1 = e0 + 4;   // this register's edge row in lane half 0 / 1
+    const int e0 = 32 * TT + acc_row(r, 0), e1 = e0 + 4;            // this register's edge row in lane half 0 / 1
     const int p0 = e0 / KE, p1 = e1 / KE;
     if (p0 == p1) {
       pm[p0] = fmaxf(pm[p0], v[r]);
@@ -54,7 +56,7 @@ __device__ __forceinline__ void fold_tile(const f32x16& v, int half, float lowes
 
 template <int KE>
 __global__ __launch_bounds__(512, 1) void edgechain_kernel(vcr_edgechain_args p, int groups_per_block) {
-  constexpr int G = 160 / KE;                              // points per 5-tile group
+  constexpr int G = edge_group_points(KE);                 // points per 5-tile group
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   Tiles& T = *reinterpret_cast<Tiles*>(smem);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -107,7 +109,7 @@ __global__ __launch_bounds__(512, 1) void edgechain_kernel(vcr_edgechain_args p,
     for (int i = 0; i < 4; ++i) {
       const f32x4 v = hp[i] + hq[i];
       st4(&T.h1[slot][16 * (w - 6) + rs + 4 * i][4 * cg],
-          f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)});
+          relu4(v));
     }
   };
 
@@ -232,6 +234,72 @@ __global__ __launch_bounds__(512, 1) void edgechain_kernel(vcr_edgechain_args p,
   for (int base = 0; base < ntiles + 3; base += 5) unroll<5>([&](auto Uc) { step(base, Uc); });
 }
 
+// Per-edge feature rows for EdgeConv CHAINS (DGCNN, model/vcrnet_model.py:104-118): conv2..conv4 act on the
+// post-ReLU per-edge tensor, so every layer is a true N*k GEMM (vcr_linear_f32 over [M*k, C] edge rows) and
+// only the first conv enjoys the F7 split.  h[(i,j)] = relu(P[nbr_ij] + Q[i]).
+__global__ __launch_bounds__(256) void edge_rows_kernel(vcr_edgerows_args p) {
+  const int lane = threadIdx.x & 63;
+  const long e = (long)xcd_chunk((int)blockIdx.x, (int)gridDim.x) * 4 + (threadIdx.x >> 6);
+  if (e >= (long)p.M * p.k) return;
+  const int pt = (int)(e / p.k);
+  const int base = (pt / p.n_per_cloud) * p.n_per_cloud;
+  const int nb = p.idx[e];
+  for (int c = lane * 4; c < p.C; c += 256) {
+    const f32x4 v = ld4(p.pq + (size_t)(base + nb) * p.ldpq + c) + ld4(p.pq + (size_t)pt * p.ldpq + p.C + c);
+    st4(p.h + (size_t)e * p.ldh + c, relu4(v));
+  }
+}
+
+// C == 64: one wave per POINT, four edge rows per step (16 lanes x 16 B each); the same pass writes the max over the
+// point's k rows (x1, vcrnet_model.py:109) and zeroes the columns that the fused maxima of conv2..conv4 will
+// accumulate into with atomic max (vcr_linear_args.segmax_out)
+__global__ __launch_bounds__(256) void edge_rows64_kernel(vcr_edgerows_args p) {
+  const int lane = threadIdx.x & 63;
+  const int pt = xcd_chunk((int)blockIdx.x, (int)gridDim.x) * 4 + (threadIdx.x >> 6);
+  if (pt >= p.M) return;
+  const int base = (pt / p.n_per_cloud) * p.n_per_cloud;
+  const int c = (lane & 15) * 4, rg = lane >> 4;
+  const f32x4 q = ld4(p.pq + (size_t)pt * p.ldpq + 64 + c);
+  f32x4 m = {0.f, 0.f, 0.f, 0.f};                        // post-ReLU values are >= 0
+  for (int j0 = 0; j0 < p.k; j0 += 4) {
+    const int j = j0 + rg;
+    if (j < p.k) {
+      const int nb = p.idx[(size_t)pt * p.k + j];
+      const f32x4 v = ld4(p.pq + (size_t)(base + nb) * p.ldpq + c) + q;
+      const f32x4 h = relu4(v);
+      st4(p.h + ((size_t)pt * p.k + j) * p.ldh + c, h);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) m[i] = fmaxf(m[i], h[i]);
+    }
+  }
+  if (p.ymax) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      m[i] = fmaxf(m[i], __shfl_xor(m[i], 16, 64));
+      m[i] = fmaxf(m[i], __shfl_xor(m[i], 32, 64));
+    }
+    float* yr = p.ymax + (size_t)pt * p.ldymax;
+    if (rg == 0) st4(yr + c, m);
+    for (int z = 64 + lane * 4; z < p.zero_to; z += 256) st4(yr + z, f32x4{0.f, 0.f, 0.f, 0.f});
+  }
+}
+
+// y[i] = max_j x[(i,j)]   (x.max(dim=-1) of vcrnet_model.py:109-118)
+__global__ __launch_bounds__(256) void segmax_kernel(vcr_segmax_args p) {
+  const int lane = threadIdx.x & 63;
+  const int pt = xcd_chunk((int)blockIdx.x, (int)gridDim.x) * 4 + (threadIdx.x >> 6);
+  if (pt >= p.M) return;
+  for (int c = lane * 4; c < p.C; c += 256) {
+    f32x4 m = ld4(p.x + ((size_t)pt * p.k) * p.ldx + c);
+    for (int j = 1; j < p.k; ++j) {
+      const f32x4 v = ld4(p.x + ((size_t)pt * p.k + j) * p.ldx + c);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) m[i] = fmaxf(m[i], v[i]);
+    }
+    st4(p.y + (size_t)pt * p.ldy + c, m);
+  }
+}
+
 }  // namespace
 
 extern "C" int vcr_edgechain_f32(const vcr_edgechain_args* a, vcr_stream_t stream) {
@@ -239,18 +307,31 @@ extern "C" int vcr_edgechain_f32(const vcr_edgechain_args* a, vcr_stream_t strea
   if (!a || !a->pq || !a->idx || !a->w2 || !a->b2 || !a->w3 || !a->b3 || !a->w4 || !a->b4 || !a->out) return VCR_EINVAL;
   if (a->M <= 0 || a->n_per_cloud <= 0 || a->ldpq < 128 || (a->ldpq & 3) || a->ldo < 512) return VCR_EINVAL;
   if (((uintptr_t)a->pq | (uintptr_t)a->w2 | (uintptr_t)a->w3 | (uintptr_t)a->w4) & 15) return VCR_EINVAL;
-  if (a->k != 20 && a->k != 40) return VCR_EUNSUPPORTED;   // the static row -> point maps (see the kernel) exist for these
-  const int G = 160 / a->k, ngroups = (a->M + G - 1) / G;
+  const int G = edge_group_points(a->k);
+  if (!G) return VCR_EUNSUPPORTED;                         // the static row -> point maps (see the kernel) exist for k = 20 / 40
+  const int ngroups = (a->M + G - 1) / G;
   const int cus = vcr_cu_count();
   const int gpb = (ngroups + cus - 1) / cus;               // groups per workgroup: one workgroup per CU, contiguous runs
-  const int grid = (ngroups + gpb - 1) / gpb;
-  const int lds = (int)sizeof(Tiles);
-  if (a->k == 20) {
-    VCR_DYN_LDS(edgechain_kernel<20>, lds);
-    hipLaunchKernelGGL(edgechain_kernel<20>, dim3(grid), dim3(512), lds, (hipStream_t)stream, *a, gpb);
-  } else {
-    VCR_DYN_LDS(edgechain_kernel<40>, lds);
-    hipLaunchKernelGGL(edgechain_kernel<40>, dim3(grid), dim3(512), lds, (hipStream_t)stream, *a, gpb);
-  }
-  return VCR_LAUNCH_RC();
+  const dim3 grid((ngroups + gpb - 1) / gpb), block(512);
+  const hipStream_t s = (hipStream_t)stream;
+  if (a->k == 20) return vcr_launch<edgechain_kernel<20>>(grid, block, sizeof(Tiles), s, *a, gpb);
+  return vcr_launch<edgechain_kernel<40>>(grid, block, sizeof(Tiles), s, *a, gpb);
+}
+
+// The chain as separate launches (any k): per-edge rows, then vcr_linear_f32 per layer, then the max over each point's rows.
+extern "C" int vcr_edgerows_f32(const vcr_edgerows_args* a, vcr_stream_t stream) {
+  if (!a || !a->pq || !a->idx || !a->h) return VCR_EINVAL;
+  if (a->M <= 0 || a->k <= 0 || a->C <= 0 || (a->C & 3) || (a->ldpq & 3) || (a->ldh & 3) || a->ldpq < 2 * a->C) return VCR_EINVAL;
+  if (a->n_per_cloud <= 0 || (a->M % a->n_per_cloud)) return VCR_EINVAL;
+  if (a->ymax && (a->C != 64 || (a->ldymax & 3) || a->ldymax < a->zero_to || (a->zero_to & 3) ||
+                  (a->zero_to && a->zero_to < 64))) return VCR_EINVAL;
+  const long rows = (long)a->M * a->k;
+  const hipStream_t s = (hipStream_t)stream;
+  if (a->C == 64) return vcr_launch<edge_rows64_kernel>(dim3((unsigned)((a->M + 3) / 4)), dim3(256), 0, s, *a);
+  return vcr_launch<edge_rows_kernel>(dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, *a);
+}
+
+extern "C" int vcr_segmax_f32(const vcr_segmax_args* a, vcr_stream_t stream) {
+  if (!a || !a->x || !a->y || a->M <= 0 || a->k <= 0 || a->C <= 0 || (a->C & 3) || (a->ldx & 3) || (a->ldy & 3)) return VCR_EINVAL;
+  return vcr_launch<segmax_kernel>(dim3((a->M + 3) / 4), dim3(256), 0, (hipStream_t)stream, *a);
 }

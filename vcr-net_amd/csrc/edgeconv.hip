@@ -15,7 +15,7 @@
 //   64 VGPRs for the whole kernel.
 // gathermax_kernel (convSN1 -> max): y[i] = relu(max_j P[nbr_ij] + Q[i]); one wave per point,
 //   whole 16-B-per-lane row loads, L2-bound.
-#include "common.h"
+#include "edge_group.h"
 
 namespace {
 
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256, 2) void edgeconv_dg_kernel(vcr_edgeconv_args p
       const int r = min(rt * 32 + rs + 8 * i, p.k - 1);
       const int nb = p.idx[(size_t)pt * p.k + r];
       const f32x4 v = ld4(p.pq + (size_t)(base + nb) * p.ldpq + ch) + q;
-      hr[i] = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+      hr[i] = relu4(v);
     }
   };
   f32x4 x1m = f32x4{0.f, 0.f, 0.f, 0.f};                 // H >= 0, so 0 is the identity of this max
@@ -60,8 +60,7 @@ __global__ __launch_bounds__(256, 2) void edgeconv_dg_kernel(vcr_edgeconv_args p
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       st4(&Hs[buf][rs + 8 * i][ch], hr[i]);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) x1m[c] = fmaxf(x1m[c], hr[i][c]);
+      x1m = max4(x1m, hr[i]);
     }
     if (rt == row_tiles - 1) {
 #pragma unroll
@@ -116,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void edgeconv_dg_kernel(vcr_edgeconv_args p
 // staged tile with the same static map.
 template <int KE>
 __global__ __launch_bounds__(256, 2) void edgeconv_dg_packed_kernel(vcr_edgeconv_args p) {
-  constexpr int G = 160 / KE;                            // points per group
+  constexpr int G = edge_group_points(KE);               // points per group
   __shared__ __attribute__((aligned(16))) float Hs[2][32][HP];
   __shared__ __attribute__((aligned(16))) float x1half[2][G][128];   // per-point column maxima of the two row halves
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -145,7 +144,7 @@ __global__ __launch_bounds__(256, 2) void edgeconv_dg_packed_kernel(vcr_edgeconv
       const int base = (pt / p.n_per_cloud) * p.n_per_cloud;
       const int nb = p.idx[(size_t)pt * KE + j];
       const f32x4 v = ld4(p.pq + (size_t)(base + nb) * p.ldpq + ch) + ld4(p.pq + (size_t)pt * p.ldpq + 128 + ch);
-      hr[i] = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+      hr[i] = relu4(v);
     }
   };
   auto commit = [&](int buf) {
@@ -184,16 +183,7 @@ __global__ __launch_bounds__(256, 2) void edgeconv_dg_packed_kernel(vcr_edgeconv
         for (int e = 0; e < 4; ++e) acc = mfma32(af[e], wf[g][e], acc);
       }
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {                     // fold the tile into the per-point maxima (static map)
-        const int row0 = 32 * t + acc_row(r, 0), row1 = row0 + 4;
-        const int p0 = row0 / KE, p1 = row1 / KE;
-        if (p0 == p1) {
-          pm[p0] = fmaxf(pm[p0], acc[r]);
-        } else {
-          pm[p0] = fmaxf(pm[p0], half ? VCR_NEG_INF : acc[r]);
-          pm[p1] = fmaxf(pm[p1], half ? acc[r] : VCR_NEG_INF);
-        }
-      }
+      for (int r = 0; r < 16; ++r) edge_fold<KE>(acc[r], t, r, half, VCR_NEG_INF, pm);   // the tile -> the per-point maxima
       if (t == 4) {
         // the group's five tiles are done: emit x2 from the MFMA maxima, x1 from the two row halves' column maxima
 #pragma unroll
@@ -207,9 +197,7 @@ __global__ __launch_bounds__(256, 2) void edgeconv_dg_packed_kernel(vcr_edgeconv
         for (int i = threadIdx.x; i < G * 32; i += 256) {
           const int q = i >> 5, c4 = (i & 31) * 4, pt = grp * G + q;
           const f32x4 lo = ld4(&x1half[0][q][c4]), hi = ld4(&x1half[1][q][c4]);
-          if (pt < p.M)
-            st4(p.x1 + (size_t)pt * p.ldx1 + c4, f32x4{fmaxf(lo[0], hi[0]), fmaxf(lo[1], hi[1]), fmaxf(lo[2], hi[2]),
-                                                        fmaxf(lo[3], hi[3])});
+          if (pt < p.M) st4(p.x1 + (size_t)pt * p.ldx1 + c4, max4(lo, hi));
         }
       }
       if (has_next) commit(cur ^ 1);
@@ -239,7 +227,7 @@ constexpr int FRAG_AHEAD = 1;                            // 1 or 2 (profiles/rou
 template <int KE>
 __global__ __launch_bounds__(256, 2) void edgeconv_dg_pipe_kernel(vcr_edgeconv_args p) {
   static_assert(KE % 2 == 0 && 160 % KE == 0, "parity split of the x1 pass");
-  constexpr int G = 160 / KE;                            // points per group
+  constexpr int G = edge_group_points(KE);               // points per group
   __shared__ __attribute__((aligned(16))) float Hs[2][32][HP];
   __shared__ __attribute__((aligned(16))) float x1half[2][G][128];   // per-point column maxima of the two row parities
   __shared__ __attribute__((aligned(16))) float x2half[2][G][128];   // per-point maxima of the MFMA rows held by the two lane halves
@@ -277,19 +265,9 @@ __global__ __launch_bounds__(256, 2) void edgeconv_dg_pipe_kernel(vcr_edgeconv_a
   };
   auto commit1 = [&](int buf, int i) {
     const f32x4 v = hr[i] + hq[i];
-    st4(&Hs[buf][rs + 8 * i][ch], f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)});
+    st4(&Hs[buf][rs + 8 * i][ch], relu4(v));
   };
   float pm[G], cm[G];                                    // per-point maxima: x2 (MFMA rows) and x1 (this thread's channel)
-  auto fold1 = [&](const f32x16& a, int t, int r) {      // accumulator register r of tile t -> the per-point maxima
-    const int row0 = 32 * t + acc_row(r, 0), row1 = row0 + 4;
-    const int p0 = row0 / KE, p1 = row1 / KE;
-    if (p0 == p1) {
-      pm[p0] = fmaxf(pm[p0], a[r]);
-    } else {
-      pm[p0] = fmaxf(pm[p0], half ? VCR_NEG_INF : a[r]);
-      pm[p1] = fmaxf(pm[p1], half ? a[r] : VCR_NEG_INF);
-    }
-  };
 
 #pragma unroll
   for (int i = 0; i < 4; ++i) load_idx1(sl.first, 0, i, nb);
@@ -328,7 +306,7 @@ __global__ __launch_bounds__(256, 2) void edgeconv_dg_pipe_kernel(vcr_edgeconv_a
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc = mfma32(af[g % 3][e], wf[g][e], acc);
         cm[(32 * t + 2 * g) / KE] = fmaxf(cm[(32 * t + 2 * g) / KE], xv[g % 3]);     // x1 pass, row 2g + parity
-        if (t > 0) fold1(accp, t - 1, g);                                           // previous tile, register g
+        if (t > 0) edge_fold<KE>(accp[g], t - 1, g, half, VCR_NEG_INF, pm);         // previous tile, register g
         if (g < 4) load_row1(t < 4 ? grp : grp_n, (t + 1) % 5, g);                  // tile s+1: rows (indices: tile s-1)
         else if (g < 8) load_idx1(t < 3 ? grp : grp_n, (t + 2) % 5, g - 4, nbn);    // tile s+2: indices
         else if (g >= 10 && g < 14) commit1(cur ^ 1, g - 10);                       // tile s+1 -> the other LDS buffer
@@ -338,7 +316,7 @@ __global__ __launch_bounds__(256, 2) void edgeconv_dg_pipe_kernel(vcr_edgeconv_a
       for (int i = 0; i < 4; ++i) nb[i] = nbn[i];
       if (t == 4) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) fold1(acc, 4, r);   // (the group's last tile: nothing left to hide it under)
+        for (int r = 0; r < 16; ++r) edge_fold<KE>(acc[r], 4, r, half, VCR_NEG_INF, pm);   // (the group's last tile: nothing left to hide it under)
         // group end: both maxima leave through LDS -- no cross-half shuffles, no per-point 4-B stores: one 16-B store of
         // x1 and one of x2 per thread
 #pragma unroll
@@ -351,8 +329,7 @@ __global__ __launch_bounds__(256, 2) void edgeconv_dg_pipe_kernel(vcr_edgeconv_a
           const int q = i >> 5, c4 = (i & 31) * 4, pt = grp * G + q;
           if (pt < p.M) {
             const f32x4 lo = ld4(&x1half[0][q][c4]), hi = ld4(&x1half[1][q][c4]);
-            st4(p.x1 + (size_t)pt * p.ldx1 + c4, f32x4{fmaxf(lo[0], hi[0]), fmaxf(lo[1], hi[1]), fmaxf(lo[2], hi[2]),
-                                                        fmaxf(lo[3], hi[3])});
+            st4(p.x1 + (size_t)pt * p.ldx1 + c4, max4(lo, hi));
             const f32x4 a0 = ld4(&x2half[0][q][c4]), a1 = ld4(&x2half[1][q][c4]);
             st4(p.x2 + (size_t)pt * p.ldx2 + c4,
                 f32x4{fmaxf(fmaxf(a0[0], a1[0]) + bias4[0], 0.f), fmaxf(fmaxf(a0[1], a1[1]) + bias4[1], 0.f),
@@ -366,8 +343,6 @@ __global__ __launch_bounds__(256, 2) void edgeconv_dg_pipe_kernel(vcr_edgeconv_a
     }
   }
 }
-
-constexpr int EDGECONV_PIPE = 1;                         // 1: the kernel above; 0: edgeconv_dg_packed_kernel (A/B builds: probe_build.py --set)
 
 __global__ __launch_bounds__(256) void gathermax_kernel(vcr_gathermax_args p) {
   const int lane = threadIdx.x & 63;
@@ -387,17 +362,13 @@ __global__ __launch_bounds__(256) void gathermax_kernel(vcr_gathermax_args p) {
     for (int u = 0; u < 20; ++u) a[u] = ld4(p.pq + (size_t)(base + id[u]) * p.ldpq + c);
     m = a[0];
 #pragma unroll
-    for (int u = 1; u < 20; ++u)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) m[i] = fmaxf(m[i], a[u][i]);
+    for (int u = 1; u < 20; ++u) m = max4(m, a[u]);
     j = 20;
     if (p.k == 40) {                                     // (BASELINE configs[4]: the second twenty likewise)
 #pragma unroll
       for (int u = 0; u < 20; ++u) a[u] = ld4(p.pq + (size_t)(base + id[20 + u]) * p.ldpq + c);
 #pragma unroll
-      for (int u = 0; u < 20; ++u)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) m[i] = fmaxf(m[i], a[u][i]);
+      for (int u = 0; u < 20; ++u) m = max4(m, a[u]);
       j = 40;
     }
   } else {
@@ -414,8 +385,7 @@ __global__ __launch_bounds__(256) void gathermax_kernel(vcr_gathermax_args p) {
   }
   for (; j < p.k; ++j) {
     const f32x4 a0 = ld4(p.pq + (size_t)(base + id[j]) * p.ldpq + c);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) m[i] = fmaxf(m[i], a0[i]);
+    m = max4(m, a0);
   }
   const f32x4 q = ld4(p.pq + (size_t)pt * p.ldpq + p.C + c);
   f32x4 y;
@@ -432,9 +402,10 @@ __global__ __launch_bounds__(256) void gathermax_kernel(vcr_gathermax_args p) {
 // delivers ~4x the L2's gather rate.  Max is exact, so the result is bit-identical.
 // (KQ = k / 4 index quads per point, read as 16-B loads one point AHEAD of the gathers that use them: the loop is a chain
 // of L2 round trips otherwise)
+constexpr __host__ __device__ int gm_pitch(int cs) { return cs + 4; }   // floats per staged row of a cs-channel slice
 template <int CS, int KQ>
 __global__ __launch_bounds__(512, 1) void gathermax_lds_kernel(vcr_gathermax_args p, int slices) {
-  constexpr int PITCH = CS + 4, LPP = CS / 4;            // floats per staged row; lanes per point
+  constexpr int PITCH = gm_pitch(CS), LPP = CS / 4;      // floats per staged row; lanes per point
   extern __shared__ __attribute__((aligned(16))) float gm_smem[];
   const int t = threadIdx.x;
   const int cloud = (int)blockIdx.x / slices, sl = (int)blockIdx.x - cloud * slices;
@@ -481,154 +452,117 @@ __global__ __launch_bounds__(512, 1) void gathermax_lds_kernel(vcr_gathermax_arg
   }
 }
 
-// Per-edge feature rows for EdgeConv CHAINS (DGCNN, model/vcrnet_model.py:104-118): conv2..conv4 act on the
-// post-ReLU per-edge tensor, so every layer is a true N*k GEMM (vcr_linear_f32 over [M*k, C] edge rows) and
-// only the first conv enjoys the F7 split.  h[(i,j)] = relu(P[nbr_ij] + Q[i]).
-__global__ __launch_bounds__(256) void edge_rows_kernel(vcr_edgerows_args p) {
-  const int lane = threadIdx.x & 63;
-  const long e = (long)xcd_chunk((int)blockIdx.x, (int)gridDim.x) * 4 + (threadIdx.x >> 6);
-  if (e >= (long)p.M * p.k) return;
-  const int pt = (int)(e / p.k);
-  const int base = (pt / p.n_per_cloud) * p.n_per_cloud;
-  const int nb = p.idx[e];
-  for (int c = lane * 4; c < p.C; c += 256) {
-    const f32x4 v = ld4(p.pq + (size_t)(base + nb) * p.ldpq + c) + ld4(p.pq + (size_t)pt * p.ldpq + p.C + c);
-    st4(p.h + (size_t)e * p.ldh + c, f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)});
-  }
+// ---- host side: check (the VCR_E* code), plan (the launch's form, decided once), run
+constexpr int EDGECONV_PIPE = 1;                         // 1: edgeconv_dg_pipe_kernel; 0: edgeconv_dg_packed_kernel (A/B builds: probe_build.py --set)
+// one resident round: two workgroups per CU (each keeps a 32 x 128 slice of W2 in registers and pays one gather chain
+// of two dependent round trips before its first tile; 1024 workgroups on 512 slots paid both twice)
+constexpr int EDGECONV_WG_PER_CU = 2;
+constexpr int EDGECONV_PADDED_MAX_GRID = 2048;           // the padded kernel (one point per item): grid-stride beyond this many
+constexpr int EDGECONV_BF16X3_MAX_GRID = 1024;           // the bf16x3 kernel (one group per item): grid-stride beyond this many
+
+// LDS-staged gathers when a 32-channel slice of one cloud's P rows fits a workgroup's LDS (N <= 1066), the grid fills
+// most of the chip (one workgroup per CU: >= 192 of them) and the 16-B accesses are aligned.  Measured on MI355X
+// (profiles/experiments/bench_gathermax.py): 32 clouds x 1024, k = 20, C = 256: 35.4 -> 23.0 us; 48 x 768: 39.5 -> 31.6;
+// 4 clouds x 1024 x 128 channels (16 workgroups): 11.1 -> 14.9, and 8-channel slices at N = 2048: 69 -> 121 -- those
+// keep the L2 gathers.  32-channel slices up to N = 1066; 16-channel slices up to N = 2048 (a whole CU's LDS per workgroup;
+// measured at 32 clouds x 2048: 62.8 -> 57.2 us, profiles/rounds4-5/r4j_bench_gathermax.txt; 8-channel slices lose everywhere:
+// 121 us there).
+constexpr size_t GM_LDS_BUDGET_AUTO32 = 150 * 1024;      // the automatic 32-channel slice: N * gm_pitch(32) * 4 B <= this (N <= 1066)
+constexpr size_t GM_LDS_MAX = 160 * 1024;                // a CU's LDS: the 16-channel slice (N <= 2048) and every forced slice
+constexpr int GM_MIN_WORKGROUPS = 192;                   // (cloud, 32-channel slice) pairs below which the L2 form is kept
+inline size_t gm_lds_bytes(int n_per_cloud, int cs) { return (size_t)n_per_cloud * gm_pitch(cs) * 4; }
+
+enum GathermaxForm { GM_L2, GM_LDS };
+struct GathermaxPlan { GathermaxForm form; int cs, slices; size_t lds; int grid; };
+
+int gathermax_check(const vcr_gathermax_args* a) {
+  if (!a || !a->pq || !a->idx || !a->y) return VCR_EINVAL;
+  if (a->M <= 0 || a->k <= 0 || a->C <= 0 || a->C > 256 || (a->C & 3)) return VCR_EINVAL;
+  if (a->n_per_cloud <= 0 || (a->M % a->n_per_cloud) || a->ldpq < 2 * a->C || (a->ldpq & 3) || (a->ldy & 3)) return VCR_EINVAL;
+  return VCR_OK;
 }
 
-// C == 64: one wave per POINT, four edge rows per step (16 lanes x 16 B each); the same pass writes the max over the
-// point's k rows (x1, vcrnet_model.py:109) and zeroes the columns that the fused maxima of conv2..conv4 will
-// accumulate into with atomic max (vcr_linear_args.segmax_out)
-__global__ __launch_bounds__(256) void edge_rows64_kernel(vcr_edgerows_args p) {
-  const int lane = threadIdx.x & 63;
-  const int pt = xcd_chunk((int)blockIdx.x, (int)gridDim.x) * 4 + (threadIdx.x >> 6);
-  if (pt >= p.M) return;
-  const int base = (pt / p.n_per_cloud) * p.n_per_cloud;
-  const int c = (lane & 15) * 4, rg = lane >> 4;
-  const f32x4 q = ld4(p.pq + (size_t)pt * p.ldpq + 64 + c);
-  f32x4 m = {0.f, 0.f, 0.f, 0.f};                        // post-ReLU values are >= 0
-  for (int j0 = 0; j0 < p.k; j0 += 4) {
-    const int j = j0 + rg;
-    if (j < p.k) {
-      const int nb = p.idx[(size_t)pt * p.k + j];
-      const f32x4 v = ld4(p.pq + (size_t)(base + nb) * p.ldpq + c) + q;
-      const f32x4 h = {fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
-      st4(p.h + ((size_t)pt * p.k + j) * p.ldh + c, h);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) m[i] = fmaxf(m[i], h[i]);
-    }
+// a->variant forces a form (1 = L2; 32 / 16 / 8 = LDS with that slice), or refuses: the one code path that can still fail
+int gathermax_plan(const vcr_gathermax_args& a, GathermaxPlan* p) {
+  const int N = a.n_per_cloud, clouds = a.M / N;
+  const bool aligned = !(((uintptr_t)a.pq | (uintptr_t)a.y | (uintptr_t)a.idx) & 15) && edge_group_points(a.k) != 0;
+  int cs = 0;
+  if (a.variant == 0) {
+    if (aligned && (long)clouds * ((a.C + 31) / 32) >= GM_MIN_WORKGROUPS)
+      cs = gm_lds_bytes(N, 32) <= GM_LDS_BUDGET_AUTO32 ? 32 : gm_lds_bytes(N, 16) <= GM_LDS_MAX ? 16 : 0;
+  } else if (a.variant == 32 || a.variant == 16 || a.variant == 8) {
+    if (!aligned || gm_lds_bytes(N, a.variant) > GM_LDS_MAX) return VCR_EUNSUPPORTED;
+    cs = a.variant;
+  } else if (a.variant != 1) {
+    return VCR_EINVAL;
   }
-  if (p.ymax) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      m[i] = fmaxf(m[i], __shfl_xor(m[i], 16, 64));
-      m[i] = fmaxf(m[i], __shfl_xor(m[i], 32, 64));
-    }
-    float* yr = p.ymax + (size_t)pt * p.ldymax;
-    if (rg == 0) st4(yr + c, m);
-    for (int z = 64 + lane * 4; z < p.zero_to; z += 256) st4(yr + z, f32x4{0.f, 0.f, 0.f, 0.f});
-  }
+  const int slices = cs ? (a.C + cs - 1) / cs : 0;       // L2 form: one wave per point, four points per workgroup
+  *p = cs ? GathermaxPlan{GM_LDS, cs, slices, gm_lds_bytes(N, cs), clouds * slices} : GathermaxPlan{GM_L2, 0, 0, 0, (a.M + 3) / 4};
+  return VCR_OK;
 }
 
-// y[i] = max_j x[(i,j)]   (x.max(dim=-1) of vcrnet_model.py:109-118)
-__global__ __launch_bounds__(256) void segmax_kernel(vcr_segmax_args p) {
-  const int lane = threadIdx.x & 63;
-  const int pt = xcd_chunk((int)blockIdx.x, (int)gridDim.x) * 4 + (threadIdx.x >> 6);
-  if (pt >= p.M) return;
-  for (int c = lane * 4; c < p.C; c += 256) {
-    f32x4 m = ld4(p.x + ((size_t)pt * p.k) * p.ldx + c);
-    for (int j = 1; j < p.k; ++j) {
-      const f32x4 v = ld4(p.x + ((size_t)pt * p.k + j) * p.ldx + c);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) m[i] = fmaxf(m[i], v[i]);
-    }
-    st4(p.y + (size_t)pt * p.ldy + c, m);
-  }
+template <int KQ>
+int gathermax_lds_run(const GathermaxPlan& p, const vcr_gathermax_args& a, hipStream_t s) {
+  const dim3 grid(p.grid), block(512);
+  if (p.cs == 32) return vcr_launch<gathermax_lds_kernel<32, KQ>>(grid, block, p.lds, s, a, p.slices);
+  if (p.cs == 16) return vcr_launch<gathermax_lds_kernel<16, KQ>>(grid, block, p.lds, s, a, p.slices);
+  return vcr_launch<gathermax_lds_kernel<8, KQ>>(grid, block, p.lds, s, a, p.slices);
 }
 
 }  // namespace
 
-extern "C" int vcr_edgerows_f32(const vcr_edgerows_args* a, vcr_stream_t stream) {
-  if (!a || !a->pq || !a->idx || !a->h) return VCR_EINVAL;
-  if (a->M <= 0 || a->k <= 0 || a->C <= 0 || (a->C & 3) || (a->ldpq & 3) || (a->ldh & 3) || a->ldpq < 2 * a->C) return VCR_EINVAL;
-  if (a->n_per_cloud <= 0 || (a->M % a->n_per_cloud)) return VCR_EINVAL;
-  if (a->ymax && (a->C != 64 || (a->ldymax & 3) || a->ldymax < a->zero_to || (a->zero_to & 3) ||
-                  (a->zero_to && a->zero_to < 64))) return VCR_EINVAL;
-  const long rows = (long)a->M * a->k;
-  if (a->C == 64)
-    hipLaunchKernelGGL(edge_rows64_kernel, dim3((unsigned)((a->M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, *a);
-  else
-    hipLaunchKernelGGL(edge_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, *a);
-  return VCR_LAUNCH_RC();
+int edgeconv_check(const vcr_edgeconv_args* a, bool bf16x3) {
+  if (!a || !a->pq || !a->idx || !a->w2 || !a->b2 || !a->x1 || !a->x2) return VCR_EINVAL;
+  if (a->M <= 0 || a->k <= 0 || a->k > 64 || a->n_per_cloud <= 0 || (a->M % a->n_per_cloud)) return VCR_EINVAL;
+  if (a->ldpq < 256 || (a->ldpq & 3) || (a->ldx1 & 3) || a->ldx1 < 128 || a->ldx2 < 128) return VCR_EINVAL;
+  if (!bf16x3) return VCR_OK;                            // (any k <= 64: the padded kernel serves what the packed ones do not)
+  if (((uintptr_t)a->w2 | (uintptr_t)a->pq | (uintptr_t)a->x1) & 15) return VCR_EINVAL;
+  return edge_group_points(a->k) ? VCR_OK : VCR_EUNSUPPORTED;
 }
 
-extern "C" int vcr_segmax_f32(const vcr_segmax_args* a, vcr_stream_t stream) {
-  if (!a || !a->x || !a->y || a->M <= 0 || a->k <= 0 || a->C <= 0 || (a->C & 3) || (a->ldx & 3) || (a->ldy & 3)) return VCR_EINVAL;
-  hipLaunchKernelGGL(segmax_kernel, dim3((a->M + 3) / 4), dim3(256), 0, (hipStream_t)stream, *a);
-  return VCR_LAUNCH_RC();
+EdgeconvPlan edgeconv_plan(const vcr_edgeconv_args& a, bool bf16x3) {
+  const int G = edge_group_points(a.k);
+  if (!G) return {EdgeconvForm::PADDED, a.M < EDGECONV_PADDED_MAX_GRID ? a.M : EDGECONV_PADDED_MAX_GRID};
+  const int ngroups = (a.M + G - 1) / G;                 // packed tiles: no padding rows
+  if (bf16x3) return {EdgeconvForm::BF16X3, ngroups < EDGECONV_BF16X3_MAX_GRID ? ngroups : EDGECONV_BF16X3_MAX_GRID};
+  const int slots = EDGECONV_WG_PER_CU * vcr_cu_count();
+  // the hand-scheduled kernel stores x2 as 16-B pieces; rows that are not 16-B aligned keep the packed kernel
+  const bool al16 = !(a.ldx2 & 3) && !(((uintptr_t)a.x1 | (uintptr_t)a.x2 | (uintptr_t)a.b2) & 15);
+  return {EDGECONV_PIPE && al16 ? EdgeconvForm::PIPE : EdgeconvForm::PACKED, ngroups < slots ? ngroups : slots};
 }
 
 extern "C" int vcr_edgeconv_f32(const vcr_edgeconv_args* a, vcr_stream_t stream) {
   vcr_stream_scope bound(stream);
-  if (!a || !a->pq || !a->idx || !a->w2 || !a->b2 || !a->x1 || !a->x2) return VCR_EINVAL;
-  if (a->M <= 0 || a->k <= 0 || a->k > 64 || a->n_per_cloud <= 0 || (a->M % a->n_per_cloud)) return VCR_EINVAL;
-  if (a->ldpq < 256 || (a->ldpq & 3) || (a->ldx1 & 3) || a->ldx1 < 128 || a->ldx2 < 128) return VCR_EINVAL;
-  if (a->k == 20 || a->k == 40) {                        // packed tiles: no padding rows
-    const int G = 160 / a->k, ngroups = (a->M + G - 1) / G;
-    // one resident round: two workgroups per CU (each keeps a 32 x 128 slice of W2 in registers and pays one gather chain
-    // of two dependent round trips before its first tile; 1024 workgroups on 512 slots paid both twice)
-    const int slots = 2 * vcr_cu_count();
-    const int grid = ngroups < slots ? ngroups : slots;
-    // the hand-scheduled kernel stores x2 as 16-B pieces; rows that are not 16-B aligned keep the kernel above
-    const bool al16 = !(a->ldx2 & 3) && !(((uintptr_t)a->x1 | (uintptr_t)a->x2 | (uintptr_t)a->b2) & 15);
-    if (EDGECONV_PIPE && al16) {
-      if (a->k == 20) hipLaunchKernelGGL(edgeconv_dg_pipe_kernel<20>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
-      else hipLaunchKernelGGL(edgeconv_dg_pipe_kernel<40>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
-    } else if (a->k == 20) hipLaunchKernelGGL(edgeconv_dg_packed_kernel<20>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
-    else hipLaunchKernelGGL(edgeconv_dg_packed_kernel<40>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
-    return VCR_LAUNCH_RC();
-  }
-  const int grid = a->M < 2048 ? a->M : 2048;
-  hipLaunchKernelGGL(edgeconv_dg_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
-  return VCR_LAUNCH_RC();
+  if (const int rc = edgeconv_check(a, false)) return rc;
+  const EdgeconvPlan p = edgeconv_plan(*a, false);
+  const dim3 grid(p.grid), block(256);
+  const hipStream_t s = (hipStream_t)stream;
+  if (p.form == EdgeconvForm::PADDED) return vcr_launch<edgeconv_dg_kernel>(grid, block, 0, s, *a);
+  if (p.form == EdgeconvForm::PIPE)
+    return a->k == 20 ? vcr_launch<edgeconv_dg_pipe_kernel<20>>(grid, block, 0, s, *a) : vcr_launch<edgeconv_dg_pipe_kernel<40>>(grid, block, 0, s, *a);
+  return a->k == 20 ? vcr_launch<edgeconv_dg_packed_kernel<20>>(grid, block, 0, s, *a) : vcr_launch<edgeconv_dg_packed_kernel<40>>(grid, block, 0, s, *a);
 }
 
 extern "C" int vcr_gathermax_f32(const vcr_gathermax_args* a, vcr_stream_t stream) {
-  if (!a || !a->pq || !a->idx || !a->y) return VCR_EINVAL;
-  if (a->M <= 0 || a->k <= 0 || a->C <= 0 || a->C > 256 || (a->C & 3)) return VCR_EINVAL;
-  if (a->n_per_cloud <= 0 || (a->M % a->n_per_cloud) || a->ldpq < 2 * a->C || (a->ldpq & 3) || (a->ldy & 3)) return VCR_EINVAL;
-  // LDS-staged gathers when a 32-channel slice of one cloud's P rows fits a workgroup's LDS (N <= 1066), the grid fills
-  // most of the chip (one workgroup per CU: >= 192 of them) and the 16-B accesses are aligned.  Measured on MI355X
-  // (profiles/experiments/bench_gathermax.py): 32 clouds x 1024, k = 20, C = 256: 35.4 -> 23.0 us; 48 x 768: 39.5 -> 31.6;
-  // 4 clouds x 1024 x 128 channels (16 workgroups): 11.1 -> 14.9, and 8-channel slices at N = 2048: 69 -> 121 -- those
-  // keep the L2 gathers.  a->variant forces a form (1 = L2; 32 / 16 / 8 = LDS with that slice), or refuses.
-  const int N = a->n_per_cloud;
-  const bool aligned = !(((uintptr_t)a->pq | (uintptr_t)a->y | (uintptr_t)a->idx) & 15) && (a->k == 20 || a->k == 40);
-  const size_t budget = 150 * 1024;
-  int cs = 0;
-  if (a->variant == 0) {
-    // 32-channel slices up to N = 1066; 16-channel slices up to N = 2048 (a whole CU's LDS per workgroup; measured at 32
-    // clouds x 2048: 62.8 -> 57.2 us, profiles/rounds4-5/r4j_bench_gathermax.txt; 8-channel slices lose everywhere: 121 us there)
-    if (aligned && (long)(a->M / N) * ((a->C + 31) / 32) >= 192)
-      cs = (size_t)N * 36 * 4 <= budget ? 32 : (size_t)N * 20 * 4 <= 160 * 1024 ? 16 : 0;
-  } else if (a->variant == 32 || a->variant == 16 || a->variant == 8) {
-    if (!aligned || (size_t)N * (a->variant + 4) * 4 > 160 * 1024) return VCR_EUNSUPPORTED;
-    cs = a->variant;
-  } else if (a->variant != 1) {
-    return VCR_EINVAL;
-  }
-  if (cs) {
-    const int slices = (a->C + cs - 1) / cs, clouds = a->M / N;
-    const size_t lds = (size_t)N * (cs + 4) * 4;
-    const dim3 grid(clouds * slices);
-#define VCR_GM(CS_, KQ_) do { VCR_DYN_LDS((gathermax_lds_kernel<CS_, KQ_>), lds); \
-      hipLaunchKernelGGL((gathermax_lds_kernel<CS_, KQ_>), grid, dim3(512), lds, (hipStream_t)stream, *a, slices); } while (0)
-    if (a->k == 20) { if (cs == 32) VCR_GM(32, 5); else if (cs == 16) VCR_GM(16, 5); else VCR_GM(8, 5); }
-    else { if (cs == 32) VCR_GM(32, 10); else if (cs == 16) VCR_GM(16, 10); else VCR_GM(8, 10); }
-#undef VCR_GM
-    return VCR_LAUNCH_RC();
-  }
-  hipLaunchKernelGGL(gathermax_kernel, dim3((a->M + 3) / 4), dim3(256), 0, (hipStream_t)stream, *a);
-  return VCR_LAUNCH_RC();
+  GathermaxPlan p;
+  if (const int rc = gathermax_check(a)) return rc;
+  if (const int rc = gathermax_plan(*a, &p)) return rc;
+  const hipStream_t s = (hipStream_t)stream;
+  if (p.form == GM_L2) return vcr_launch<gathermax_kernel>(dim3(p.grid), dim3(256), 0, s, *a);
+  return a->k == 20 ? gathermax_lds_run<5>(p, *a, s) : gathermax_lds_run<10>(p, *a, s);
+}
+
+// Host-only, library-internal (test_abi.py, edge_plan_sweep.cpp): the entry point's code and launch form; nothing is launched.
+extern "C" int vcr_edgeconv_forms_(const vcr_edgeconv_args* a, int bf16x3, int* form, int* grid) {
+  if (const int rc = edgeconv_check(a, bf16x3 != 0)) return rc;
+  const EdgeconvPlan p = edgeconv_plan(*a, bf16x3 != 0);
+  *form = (int)p.form; *grid = p.grid;
+  return VCR_OK;
+}
+extern "C" int vcr_gathermax_forms_(const vcr_gathermax_args* a, int* form, int* cs, int* grid, int* lds_bytes) {
+  GathermaxPlan p;
+  if (const int rc = gathermax_check(a)) return rc;
+  if (const int rc = gathermax_plan(*a, &p)) return rc;
+  *form = (int)p.form; *cs = p.cs; *grid = p.grid; *lds_bytes = (int)p.lds;
+  return VCR_OK;
 }

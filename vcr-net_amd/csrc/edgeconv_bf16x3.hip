@@ -12,6 +12,7 @@
 //   cross-lane reduction per point, as soon as its last row has passed), so it is bit-identical to the fp32 kernel's and
 //   needs no column pass over LDS.
 #include "bf16x3.h"
+#include "edge_group.h"
 
 namespace {
 
@@ -19,7 +20,7 @@ constexpr int HPB = 136;   // H plane row pitch in bf16 (272 B): the 16-lane ds_
 
 template <int KE>
 __global__ __launch_bounds__(256, 2) void edgeconv_dg_packed_bf16x3_kernel(vcr_edgeconv_args p) {
-  constexpr int G = 160 / KE;                            // points per group
+  constexpr int G = edge_group_points(KE);               // points per group
   __shared__ __attribute__((aligned(16))) short Hs[2][3][32][HPB];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int half = lane >> 5, l31 = lane & 31;
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(256, 2) void edgeconv_dg_packed_bf16x3_kernel(vcr_e
       const int pt = min(grp * G + e / KE, p.M - 1);
       const int base = (pt / p.n_per_cloud) * p.n_per_cloud;
       const f32x4 v = ld4(p.pq + (size_t)(base + nb[i]) * p.ldpq + ch) + ld4(p.pq + (size_t)pt * p.ldpq + 128 + ch);
-      hr[i] = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+      hr[i] = relu4(v);
     }
   };
   float cm[G][4];                                        // x1: running max of this thread's rows, per point (H >= 0)
@@ -141,16 +142,7 @@ __global__ __launch_bounds__(256, 2) void edgeconv_dg_packed_bf16x3_kernel(vcr_e
         acc = mfma6(fa, wh[s], wm[s], wl[s], acc);
       }
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {                     // fold the tile into the per-point maxima (static map)
-        const int row0 = 32 * t + acc_row(r, 0), row1 = row0 + 4;
-        const int p0 = row0 / KE, p1 = row1 / KE;
-        if (p0 == p1) {
-          pm[p0] = fmaxf(pm[p0], acc[r]);
-        } else {
-          pm[p0] = fmaxf(pm[p0], half ? VCR_NEG_INF : acc[r]);
-          pm[p1] = fmaxf(pm[p1], half ? acc[r] : VCR_NEG_INF);
-        }
-      }
+      for (int r = 0; r < 16; ++r) edge_fold<KE>(acc[r], t, r, half, VCR_NEG_INF, pm);   // the tile -> the per-point maxima
       if (t == 4) {
         // the group's five tiles are done: x2 from the MFMA maxima
 #pragma unroll
@@ -172,14 +164,9 @@ __global__ __launch_bounds__(256, 2) void edgeconv_dg_packed_bf16x3_kernel(vcr_e
 // Same contract as vcr_edgeconv_f32 for k = 20 / 40 (the path's values); other k: VCR_EUNSUPPORTED (the caller keeps
 // the fp32 kernel).  x1 is bit-identical to vcr_edgeconv_f32's, x2 agrees to fp32-GEMM rounding.
 extern "C" int vcr_edgeconv_bf16x3_f32(const vcr_edgeconv_args* a, vcr_stream_t stream) {
-  if (!a || !a->pq || !a->idx || !a->w2 || !a->b2 || !a->x1 || !a->x2) return VCR_EINVAL;
-  if (a->M <= 0 || a->k <= 0 || a->k > 64 || a->n_per_cloud <= 0 || (a->M % a->n_per_cloud)) return VCR_EINVAL;
-  if (a->ldpq < 256 || (a->ldpq & 3) || (a->ldx1 & 3) || a->ldx1 < 128 || a->ldx2 < 128) return VCR_EINVAL;
-  if (((uintptr_t)a->w2 | (uintptr_t)a->pq | (uintptr_t)a->x1) & 15) return VCR_EINVAL;
-  if (a->k != 20 && a->k != 40) return VCR_EUNSUPPORTED;
-  const int G = 160 / a->k, ngroups = (a->M + G - 1) / G;
-  const int grid = ngroups < 1024 ? ngroups : 1024;
-  if (a->k == 20) hipLaunchKernelGGL(edgeconv_dg_packed_bf16x3_kernel<20>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
-  else hipLaunchKernelGGL(edgeconv_dg_packed_bf16x3_kernel<40>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
-  return VCR_LAUNCH_RC();
+  if (const int rc = edgeconv_check(a, true)) return rc;
+  const dim3 grid(edgeconv_plan(*a, true).grid), block(256);
+  const hipStream_t s = (hipStream_t)stream;
+  if (a->k == 20) return vcr_launch<edgeconv_dg_packed_bf16x3_kernel<20>>(grid, block, 0, s, *a);
+  return vcr_launch<edgeconv_dg_packed_bf16x3_kernel<40>>(grid, block, 0, s, *a);
 }

@@ -6,7 +6,7 @@
 // (transformer.py:269-270).  With that ordering the decoder stream for batch b is "the cloud itself"
 // and its encoder memory is the OTHER cloud's, i.e. batch (b + B) mod 2B -- a kv_batch_shift in the
 // attention kernel, no data movement.
-#include "common.h"
+#include "edge_group.h"
 
 namespace {
 
@@ -586,7 +586,7 @@ int forward_impl(const vcr_vcrnet_weights* W, const vcr_vcrnet_io* io, void* wor
         return vcr_linear_f32(&a, R.stream);
       });
     };
-    if (k == 20 || k == 40) {
+    if (edge_group_points(k)) {
       // the path's k: the whole chain in one kernel, the per-edge activations stay in LDS (edgechain.hip)
       R.run(NM("edgeconv:dg_chain"), [&] {
         vcr_edgechain_args a{w.pq1, 128, w.idx3, k, Mq, N, W->dgcnn.c2_w, W->dgcnn.c2_b, W->dgcnn.c3_w, W->dgcnn.c3_b,
@@ -664,7 +664,7 @@ int forward_impl(const vcr_vcrnet_weights* W, const vcr_vcrnet_io* io, void* wor
   R.run(NM("edgeconv:dg1_dg2"), [&] {
     vcr_edgeconv_args a{w.pq1, 256, w.idx1, k, Mq, N, W->dg2_w, W->dg2_b, w.cat, 512, w.cat + 128, 512};
     // (linear_mode 1 / 2: convDG2 as exact bf16 splits at the path's k; other k keep the fp32 kernel)
-    return W->linear_mode != 0 && (k == 20 || k == 40) ? vcr_edgeconv_bf16x3_f32(&a, R.stream) : vcr_edgeconv_f32(&a, R.stream);
+    return W->linear_mode != 0 && edge_group_points(k) ? vcr_edgeconv_bf16x3_f32(&a, R.stream) : vcr_edgeconv_f32(&a, R.stream);
   });
   R.linear(NM("linear:sn1_pq"), w.cat + 128, 512, W->sn1_wpq, SP(sn1_pq), W->sn1_bpq, w.pq3, 512, Mq, 512, 128, 0);
   R.run(NM("gathermax:sn1"), [&] {

@@ -575,12 +575,16 @@ def rowside(x, xyz4, scale=1.0):
 
 
 @_guarded
-def edgeconv(pq, idx, n_per_cloud, w2, b2, bf16x3=False):
+def edgeconv(pq, idx, n_per_cloud, w2, b2, bf16x3=False, out=None):
+    """out = (x1, x2): write into these [M, 128] row views (unit column stride, any row pitch and alignment the entry point
+    takes) instead of fresh tensors."""
     M = pq.shape[0]
     k = idx.shape[-1]
-    x1, x2 = _f32(M, 128, device=pq.device), _f32(M, 128, device=pq.device)
+    x1, x2 = out if out is not None else (_f32(M, 128, device=pq.device), _f32(M, 128, device=pq.device))
+    if out is not None and any(t.shape != (M, 128) or t.stride(1) != 1 or t.dtype != torch.float32 for t in out):
+        raise VcrHipError("edgeconv: out = (x1, x2) must be fp32 [M, 128] row views")
     call("vcr_edgeconv_bf16x3_f32" if bf16x3 else "vcr_edgeconv_f32", EdgeconvArgs(ptr(pq), pq.stride(0), ptr(idx), k, M, n_per_cloud, ptr(w2), ptr(b2),
-                                          ptr(x1), 128, ptr(x2), 128))
+                                          ptr(x1), x1.stride(0), ptr(x2), x2.stride(0)))
     return x1, x2
 
 
