@@ -53,8 +53,6 @@ def main():
                                    w8 if Cc == 64 else 0)
                 a.tie_defer = 1
                 args.append(a); keep.append((idx, ties_))
-            L.vcr_knn_pair_f32.argtypes = [C.POINTER(native.KnnArgs), C.POINTER(native.KnnArgs), C.c_void_p]
-            L.vcr_knn_pair_f32.restype = C.c_int
             fn = lambda: native.check(L.vcr_knn_pair_f32(C.byref(args[0]), C.byref(args[1]), C.c_void_p(native.stream_ptr())), "pair")
             print(f"B={B:3d} N={N:5d} k={k:2d} pair launch, feature-space kernel = {'16' if w8 == 8 else '32'}-query waves: {bench(fn):8.1f} us")
 

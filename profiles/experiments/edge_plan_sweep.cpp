@@ -2,7 +2,7 @@
 // gathermax_plan) through the library-internal reporters vcr_edgeconv_forms_ and vcr_gathermax_forms_: one fixed-size binary
 // record per argument set on stdout, the number of sets on stderr.  Two builds of the library plan alike iff their recordings
 // are byte-identical:
-//   c++ -O2 -std=c++17 -I include profiles/experiments/edge_plan_sweep.cpp -ldl -o /tmp/edge_plan_sweep
+//   c++ -O2 -std=c++17 -I include -I vcr-net_amd/csrc profiles/experiments/edge_plan_sweep.cpp -ldl -o /tmp/edge_plan_sweep
 //   cmp <(/tmp/edge_plan_sweep old/libvcr_hip.so) <(/tmp/edge_plan_sweep vcr-net_amd/libvcr_hip.so)
 // No GPU is needed (the library then plans for 256 CUs); pointers are made-up addresses, never dereferenced on the host.
 #include <dlfcn.h>
@@ -10,10 +10,10 @@
 #include <stdio.h>
 #include <string.h>
 #include <vector>
-#include "vcr_hip.h"
+#include "vcr_internal.h"
 
-typedef int (*ec_fn)(const vcr_edgeconv_args*, int, int*, int*);
-typedef int (*gm_fn)(const vcr_gathermax_args*, int*, int*, int*, int*);
+typedef decltype(&vcr_edgeconv_forms_) ec_fn;
+typedef decltype(&vcr_gathermax_forms_) gm_fn;
 static ec_fn ec_forms;
 static gm_fn gm_forms;
 static long nsets = 0;

@@ -1,7 +1,7 @@
 // Host-only sweep of the fp32 linear's launch planner (csrc/linear.hip: linear_plan) through the library-internal reporter
 // vcr_linear_forms_ and vcr_linear_config: one fixed-size binary record per argument set on stdout, the number of sets on
 // stderr.  Two builds of the library plan alike iff their recordings are byte-identical:
-//   c++ -O2 -std=c++17 -I include profiles/experiments/linear_plan_sweep.cpp -ldl -o /tmp/linear_plan_sweep
+//   c++ -O2 -std=c++17 -I include -I vcr-net_amd/csrc profiles/experiments/linear_plan_sweep.cpp -ldl -o /tmp/linear_plan_sweep
 //   cmp <(/tmp/linear_plan_sweep old/libvcr_hip.so) <(/tmp/linear_plan_sweep vcr-net_amd/libvcr_hip.so)
 // No GPU is needed (the library then plans for 256 CUs); pointers are made-up addresses, never dereferenced on the host.
 #include <dlfcn.h>
@@ -9,10 +9,10 @@
 #include <stdio.h>
 #include <string.h>
 #include <vector>
-#include "vcr_hip.h"
+#include "vcr_internal.h"
 
-typedef int (*forms_fn)(const vcr_linear_args*, const vcr_linear_args*, int*, int*, int*);
-typedef int (*config_fn)(const vcr_linear_args*);
+typedef decltype(&vcr_linear_forms_) forms_fn;
+typedef decltype(&vcr_linear_config) config_fn;
 static forms_fn forms;
 static config_fn config;
 static long nsets = 0;

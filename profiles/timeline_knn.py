@@ -1,7 +1,6 @@
 #!/usr/bin/env python
 """Experiment: phase breakdown of the kNN kernels (wave 0 of every workgroup of cloud 0 accumulates the 100 MHz wall
 clock per phase).  Needs the probe library scratch/libvcr_probe.so (python profiles/experiments/probe_build.py)."""
-import ctypes as C
 import os
 import sys
 
@@ -18,8 +17,6 @@ def main():
     from vcrnet_amd import native
     native.LIB_PATH = LIB
     L = native.lib()
-    L.vcr_dbg_probe_knn.argtypes = [C.c_void_p, C.c_int]
-    L.vcr_dbg_probe_knn.restype = C.c_int
     g = torch.Generator().manual_seed(0)
     full = np.zeros((4096, 32), np.uint64)
     names = {"feat64": ["prefetch issue", "MFMA wait+filter", "make_room", "pick", "log push", "drain", "-", "-"],

@@ -6,7 +6,6 @@ tile's k loop / at the end) and prints the distribution per phase for the persis
   python profiles/timeline_linear.py build     # in the build container (hipcc): writes scratch/libvcr_probe.so
   python profiles/timeline_linear.py           # on the GPU box
 """
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -28,8 +27,6 @@ def main():
     from vcrnet_amd import native
     native.LIB_PATH = LIB
     L = native.lib()
-    L.vcr_dbg_probe_linear.argtypes = [C.c_void_p, C.c_int]
-    L.vcr_dbg_probe_linear.restype = C.c_int
     M = 2 * 16 * 1024
     full = np.zeros((4096, 32), np.uint64)                # [workgroup][16 wall-clock stamps | 16 shader-clock stamps]
     for name, N, K, res, ln, st in [("qkv", 1536, 512, 0, 1, 0), ("wo", 512, 512, 1, 0, 1), ("ffn2", 512, 1024, 1, 0, 1),

@@ -2,7 +2,7 @@
 """Where an sdpa workgroup's time goes (probe build: python profiles/experiments/probe_build.py; wave 0 stamps the 100 MHz
 clock at start / after the prologue (Q in registers, first K | V tile staged) / after the key loop / after the output
 stores are acknowledged).  Run on the GPU box."""
-import ctypes as C, math, os, sys
+import math, os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -10,7 +10,6 @@ import vcrnet_amd  # noqa
 from vcrnet_amd import native
 native.LIB_PATH = os.path.join(ROOT, "scratch", "libvcr_probe.so")
 L = native.lib()
-L.vcr_dbg_probe_attention.argtypes = [C.c_void_p, C.c_int]
 full = np.zeros((4096, 32), np.uint64)
 for nb, N in ((32, 1024), (32, 2048)):
     qkv = torch.randn(nb * N, 1536, device="cuda")

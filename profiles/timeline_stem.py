@@ -1,7 +1,6 @@
 #!/usr/bin/env python
 """Experiment: phase breakdown of the fused stem launch (waves 0 and 7 of every workgroup accumulate the 100 MHz wall
 clock per phase).  Needs the probe library scratch/libvcr_probe.so (python profiles/experiments/probe_build.py)."""
-import ctypes as C
 import os
 import sys
 
@@ -18,8 +17,6 @@ def main():
     from vcrnet_amd import native
     native.LIB_PATH = LIB
     L = native.lib()
-    L.vcr_dbg_probe_pointwise.argtypes = [C.c_void_p, C.c_int]
-    L.vcr_dbg_probe_pointwise.restype = C.c_int
     g = torch.Generator().manual_seed(0)
     w1 = torch.randn(64, 3, generator=g).cuda(); b1 = torch.randn(64, generator=g).cuda()
     w2 = (torch.randn(64, 64, generator=g) / 8).cuda(); b2 = torch.randn(64, generator=g).cuda()

@@ -9,6 +9,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "vcr_hip.h")
+INTERNAL_HEADER = os.path.join(ROOT, "vcr-net_amd", "csrc", "vcr_internal.h")
 
 
 @pytest.fixture(scope="module")
@@ -19,9 +20,31 @@ def lib():
     return native.lib()
 
 
-def declared_symbols():
-    src = open(HEADER).read()
+def declared_symbols(header=None):
+    src = open(header or HEADER).read()
     return sorted(set(re.findall(r"\b(vcr_[a-z0-9_]+)\s*\(", src)))
+
+
+def prototypes(header):
+    """{name: (return type, [parameter types])} of every `ret vcr_name(params);` of a header, comments and preprocessor lines
+    stripped; a type is its base name with one '*' per level of indirection, `const` and parameter names dropped."""
+    src = re.sub(r"/\*.*?\*/", " ", open(header).read(), flags=re.S)
+    src = re.sub(r"//[^\n]*", " ", src)
+    src = re.sub(r"^\s*#.*$", " ", src, flags=re.M)
+
+    def ctype(text, named):
+        tok = text.replace("*", " * ").split()
+        if named and len(tok) >= 2 and tok[-1] != "*":       # a type is one word or ends in '*': what follows is the name
+            tok = tok[:-1]
+        tok = [t for t in tok if t != "const"]
+        assert len(tok) >= 1 and all(t == "*" for t in tok[1:]), text
+        return tok[0] + "*" * (len(tok) - 1)
+    out = {}
+    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\**)\s*\b(vcr_\w+)\s*\(([^()]*)\)\s*;", src):
+        assert name not in out, name
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        out[name] = (ctype(ret, False), [ctype(p, True) for p in params])
+    return out
 
 
 def test_header_symbols_exported(lib):
@@ -45,19 +68,12 @@ def test_ctypes_structs_match_the_c_layout(tmp_path):
     import subprocess
     import vcrnet_amd  # noqa: F401
     from vcrnet_amd import native
-    pairs = {"vcr_pointwise_args": native.PointwiseArgs, "vcr_knn_args": native.KnnArgs,
-             "vcr_knn_order_args": native.KnnOrderArgs,
-             "vcr_linear_args": native.LinearArgs, "vcr_layernorm_args": native.LayerNormArgs,
-             "vcr_rowside_args": native.RowsideArgs, "vcr_edgeconv_args": native.EdgeconvArgs,
-             "vcr_gathermax_args": native.GathermaxArgs, "vcr_edgerows_args": native.EdgerowsArgs,
-             "vcr_edgechain_args": native.EdgechainArgs,
-             "vcr_segmax_args": native.SegmaxArgs, "vcr_sdpa_args": native.SdpaArgs,
-             "vcr_keymass_args": native.KeymassArgs, "vcr_softcorr_args": native.SoftcorrArgs,
-             "vcr_pairscore_args": native.PairscoreArgs, "vcr_scoremass_args": native.ScoremassArgs,
-             "vcr_rankselect_args": native.RankselectArgs, "vcr_gather_args": native.GatherArgs,
-             "vcr_rigid_svd_args": native.RigidSvdArgs, "vcr_icp_args": native.IcpArgs,
-             "vcr_make_pairs_args": native.MakePairsArgs, "vcr_pose_step_args": native.PoseStepArgs, "vcr_vcrnet_weights": native.VcrnetWeights,
-             "vcr_vcrnet_io": native.VcrnetIo, "vcr_trace": native.Trace}
+    pairs = native.STRUCTS
+    # every mirror native.py defines is in the map, or is a member (by value) of a mirror that is
+    mirrors = {c for c in vars(native).values() if isinstance(c, type) and issubclass(c, ctypes.Structure)
+               and c.__module__ == native.__name__ and not c.__name__.startswith("_")}
+    nested = {t for ct in pairs.values() for _, t in ct._fields_ if isinstance(t, type) and issubclass(t, ctypes.Structure)}
+    assert mirrors == set(pairs.values()) | nested, sorted(c.__name__ for c in mirrors ^ (set(pairs.values()) | nested))
     hdr = open(HEADER).read()
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(void) {']
     expect = []
@@ -79,6 +95,39 @@ def test_ctypes_structs_match_the_c_layout(tmp_path):
     assert len(got) == len(expect)
     bad = [(c, f, e, g) for (c, f, e), g in zip(expect, got) if e != g]
     assert not bad, bad
+
+
+def test_ctypes_signatures_match_the_header(lib):
+    """native.SIGNATURES against the prototypes: PUBLIC names exactly what include/vcr_hip.h declares, INTERNAL what
+    csrc/vcr_internal.h declares; per prototype the arity, the return type, every scalar exactly, every struct pointer as
+    POINTER of the mirror native.STRUCTS names, every other pointer (and vcr_stream_t) as some pointer-typed parameter.  And
+    lib() has applied the table: a restype nobody set would truncate a size_t, a parameter added to the header would go
+    unnoticed until a GPU run went wrong."""
+    from vcrnet_amd import native
+    scalars = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "long": ctypes.c_long, "float": ctypes.c_float}
+    returns = dict(scalars, **{"char*": ctypes.c_char_p})
+    pointer_like = lambda t: t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer)  # noqa: E731
+    assert set(native.SIGNATURES) == set(native.PUBLIC) | set(native.INTERNAL) and not set(native.PUBLIC) & set(native.INTERNAL)
+    for header, table in ((HEADER, native.PUBLIC), (INTERNAL_HEADER, native.INTERNAL)):
+        protos = prototypes(header)
+        assert set(protos) == set(table) == set(declared_symbols(header)), \
+            sorted(set(protos) ^ set(table)) + sorted(set(protos) ^ set(declared_symbols(header)))
+        for name, (ret, params) in protos.items():
+            res, args = table[name]
+            assert res is returns[ret], (name, ret, res)
+            assert len(args) == len(params), (name, params, args)
+            for i, (c, t) in enumerate(zip(params, args)):
+                if c in scalars:
+                    assert t is scalars[c], (name, i, c, t)
+                elif c.startswith("vcr_") and c != "vcr_stream_t":
+                    assert c.endswith("*") and not c.endswith("**"), (name, i, c)
+                    assert t is ctypes.POINTER(native.STRUCTS[c[:-1]]), (name, i, c, t)
+                else:
+                    assert c == "vcr_stream_t" or c.endswith("*"), (name, i, c)       # no scalar type this test does not know
+                    assert pointer_like(t), (name, i, c, t)
+            fn = getattr(lib, name)
+            assert fn.restype is res and list(fn.argtypes or []) == list(args), name
+    assert len(native.PUBLIC) == 51 and len(native.INTERNAL) == 6
 
 
 def test_argument_errors_do_not_need_a_gpu(lib):
@@ -123,8 +172,6 @@ def test_sized_structs_refuse_what_they_cannot_read(lib):
     the mandatory part, or more than the library knows is an argument error; a SHORTER struct from an older header is served,
     its missing tail read as zeros -- the library never reads past what the caller said it passed."""
     from vcrnet_amd import native
-    lib.vcr_vcrnet_workspace_bytes.restype = ctypes.c_size_t
-    lib.vcr_knn_ties_inline.argtypes = [ctypes.POINTER(native.KnnArgs)]
     w = native.VcrnetWeights()
     assert w.struct_bytes == ctypes.sizeof(native.VcrnetWeights)
     w.E, w.F, w.heads, w.k, w.has_pointer = 512, 1024, 4, 20, 1
@@ -179,7 +226,6 @@ def test_workspace_plan_sizes_of_the_baseline_configs(lib):
     sizes of the BASELINE configs are pinned here -- a buffer registered with too long a life, or the bump allocator coming
     back, shows up as a size regression without a GPU.  (Round 4's bump layout: 1.5 GB at configs[1], ~12 GB at configs[4].)"""
     from vcrnet_amd import native
-    lib.vcr_vcrnet_workspace_bytes.restype = ctypes.c_size_t
 
     def gib(B, N, k=20, merged=True, **kw):
         w = native.VcrnetWeights()
@@ -205,9 +251,6 @@ def test_host_side_dispatch_logic_without_a_gpu(lib):
     scratch the replay of long rows needs, the limits that are refused rather than degraded, argument errors of the
     paired linear and the grouped / indexed attention."""
     from vcrnet_amd import native
-    lib.vcr_knn_ties_inline.argtypes = [ctypes.POINTER(native.KnnArgs)]
-    lib.vcr_knn_ties_inline.restype = ctypes.c_int
-    lib.vcr_knn_tie_work_bytes.argtypes, lib.vcr_knn_tie_work_bytes.restype = [ctypes.c_int], ctypes.c_size_t
 
     def knn_args(B, N, Cc, k, ties=True, waves=0):
         a = native.KnnArgs()
@@ -229,8 +272,6 @@ def test_host_side_dispatch_logic_without_a_gpu(lib):
     assert lib.vcr_knn_f32(ctypes.byref(a), None) == -3
     assert lib.vcr_knn_f32(ctypes.byref(knn_args(4, 1024, 4, 63)), None) == -3 # library limit k <= 62
     assert lib.vcr_knn_f32(ctypes.byref(knn_args(4, 1024, 4, 20, waves=3)), None) == -1
-    lib.vcr_linear_pair_f32.argtypes = [ctypes.POINTER(native.LinearArgs), ctypes.POINTER(native.LinearArgs), ctypes.c_void_p]
-    lib.vcr_linear_pair_f32.restype = ctypes.c_int
     la = native.LinearArgs()
     assert lib.vcr_linear_pair_f32(ctypes.byref(la), ctypes.byref(la), None) == -1
     la.x, la.w, la.y, la.ldx, la.ldy, la.M, la.N, la.K = 0x1000, 0x2000, 0x3000, 64, 64, 128, 64, 64
@@ -254,7 +295,6 @@ def test_linear_launch_choice_against_the_recorded_sweep(lib):
     import os
     import re
     from vcrnet_amd import native
-    lib.vcr_linear_config.argtypes, lib.vcr_linear_config.restype = [ctypes.POINTER(native.LinearArgs)], ctypes.c_int
 
     def cfg(M, N, K, residual, variant=0):
         a = native.LinearArgs()
@@ -291,8 +331,6 @@ def test_sdpa_launch_form_of_the_quoted_shapes(lib):
     """vcr_sdpa_forms_ (host-only, library-internal): what sdpa_plan makes of the attention launches DESIGN and the tests quote,
     on 256 CUs -- MI355X's count, and the one the library assumes without a GPU."""
     from vcrnet_amd import native
-    lib.vcr_sdpa_forms_.argtypes = [ctypes.POINTER(native.SdpaArgs), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-    lib.vcr_sdpa_forms_.restype = ctypes.c_int
 
     def form(nb, nq, nk, out=True, groups=1, split_floats=0, key_index=False):
         a = native.SdpaArgs()
@@ -329,8 +367,6 @@ def test_linear_pair_launch_form_of_the_quoted_shapes(lib):
     tests quote, on 256 CUs -- whether the two halves are one launch, and per half (LDS-DMA family, tile rows, k-slab, MFMA
     shape, grid[, dynamic LDS bytes]).  K = 512; "res" = a residual and stats_out on that half."""
     from vcrnet_amd import native
-    lib.vcr_linear_forms_.argtypes = [ctypes.POINTER(native.LinearArgs)] * 2 + [ctypes.POINTER(ctypes.c_int)] * 3
-    lib.vcr_linear_forms_.restype = ctypes.c_int
 
     def half(M, N, res=False, stats=None, variant=0):
         a = native.LinearArgs()
@@ -377,8 +413,6 @@ def test_edgeconv_launch_form_of_the_quoted_shapes(lib):
     DESIGN and the tests quote, on 256 CUs: (code, form, grid) with form 0 = padded, 1 = packed, 2 = the hand-scheduled packed
     kernel, 3 = bf16x3."""
     from vcrnet_amd import native
-    I = ctypes.POINTER(ctypes.c_int)
-    lib.vcr_edgeconv_forms_.argtypes, lib.vcr_edgeconv_forms_.restype = [ctypes.POINTER(native.EdgeconvArgs), ctypes.c_int, I, I], ctypes.c_int
 
     def form(M, N, k, bf16x3=False, pq=0x10000, b2=0x40000, x2=0x60000, ldx2=128):
         a = native.EdgeconvArgs(pq, 256, 0x20000, k, M, N, 0x30000, b2, 0x50000, 128, x2, ldx2)   # (never dereferenced on the host)
@@ -405,8 +439,6 @@ def test_gathermax_launch_form_of_the_quoted_shapes(lib):
     with form 0 = gathers through L2 (one wave per point), 1 = out of LDS (one workgroup per cloud and slice, N x (slice + 4)
     floats)."""
     from vcrnet_amd import native
-    I = ctypes.POINTER(ctypes.c_int)
-    lib.vcr_gathermax_forms_.argtypes, lib.vcr_gathermax_forms_.restype = [ctypes.POINTER(native.GathermaxArgs), I, I, I, I], ctypes.c_int
 
     def form(B, N, k=20, C=256, variant=0, idx=0x20000):
         a = native.GathermaxArgs(0x10000, 2 * C, C, idx, k, B * N, N, 0x30000, C, variant, None)

@@ -535,7 +535,6 @@ def _edgeconv_form(nat, pq, idx, N, w2, b2, x1, x2):
     a = nat.EdgeconvArgs(nat.ptr(pq), pq.stride(0), nat.ptr(idx), idx.shape[-1], pq.shape[0], N, nat.ptr(w2), nat.ptr(b2),
                          nat.ptr(x1), x1.stride(0), nat.ptr(x2), x2.stride(0))
     fn = nat.lib().vcr_edgeconv_forms_
-    fn.argtypes = [ctypes.POINTER(nat.EdgeconvArgs), ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     form, grid = ctypes.c_int(-1), ctypes.c_int(-1)
     return fn(ctypes.byref(a), 0, ctypes.byref(form), ctypes.byref(grid)), form.value, grid.value
 
@@ -1009,8 +1008,6 @@ def test_knn_in_launch_tie_replay_through_global_slots(nat, B, N, k, ordered):
     c1 = nat.knn(x4, None, k, tie_slots=True)
     assert torch.equal(c1, nat.knn(x4, None, k))
     L = nat.lib()
-    L.vcr_knn_ties_inline.argtypes, L.vcr_knn_ties_inline.restype = [C.POINTER(nat.KnnArgs)], C.c_int
-    L.vcr_knn_tie_slot_bytes.argtypes, L.vcr_knn_tie_slot_bytes.restype = [C.c_int, C.c_int], C.c_size_t
     a = nat.KnnArgs(0x1000, 4, None, B, N, 4, k, 0x2000, 0x3000, B * N)
     lds_fits = N <= 2300 and k <= 20
     assert L.vcr_knn_ties_inline(C.byref(a)) == (1 if lds_fits and B * ((N + 15) // 16) >= 1024 else 0)
@@ -1093,8 +1090,6 @@ def test_linear_pair_equals_two_launches(nat):
     g = torch.Generator().manual_seed(5)
     M, K = 3000, 512
     L = nat.lib()
-    L.vcr_linear_pair_f32.argtypes = [C.POINTER(nat.LinearArgs), C.POINTER(nat.LinearArgs), C.c_void_p]
-    L.vcr_linear_pair_f32.restype = C.c_int
     for (Na, Nb, res_b) in ((512, 512, True), (1024, 512, False), (512, 256, True)):
         xa, xb = dev(torch.randn(M, K, generator=g)), dev(torch.randn(M + 77, K, generator=g))
         wa, wb = dev(torch.randn(Na, K, generator=g) / 22), dev(torch.randn(Nb, K, generator=g) / 22)

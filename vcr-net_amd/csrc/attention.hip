@@ -10,6 +10,7 @@
 // holds key (r&3)+8(r>>2)+4*half, the A operand for that k-step is V[that key][d] -- no LDS round trip
 // and no cross-lane movement between the two MFMA chains.
 #include "common.h"
+#include "vcr_internal.h"
 
 namespace {
 

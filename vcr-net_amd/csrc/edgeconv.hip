@@ -16,6 +16,7 @@
 // gathermax_kernel (convSN1 -> max): y[i] = relu(max_j P[nbr_ij] + Q[i]); one wave per point,
 //   whole 16-B-per-lane row loads, L2-bound.
 #include "edge_group.h"
+#include "vcr_internal.h"
 
 namespace {
 

@@ -7,6 +7,7 @@
 // and its encoder memory is the OTHER cloud's, i.e. batch (b + B) mod 2B -- a kv_batch_shift in the
 // attention kernel, no data movement.
 #include "edge_group.h"
+#include "vcr_internal.h"
 
 namespace {
 
@@ -115,11 +116,6 @@ inline int merged_encdec(const vcr_vcrnet_weights* W) {
   return W->has_pointer == 1 && (W->linear_mode == 0 || W->split.encdec_qkv) && W->fold_encdec_qkv.w && W->fold_encdec_qkv.colsum &&
          W->fold_encdec_qkv.bias;
 }
-
-extern "C" int vcr_linear_forms_(const vcr_linear_args* a, const vcr_linear_args* b, int* one_launch, int* form_a, int* form_b);   // linear.hip
-extern "C" int vcr_knn_forms_(const vcr_knn_args* a, const vcr_knn_args* b, int* ordered, int* inline_a, int* inline_b);  // knn.hip
-extern "C" int vcr_sdpa_forms_(const vcr_sdpa_args* a, int* nsplit, int* persistent);   // attention.hip
-extern "C" long vcr_sdpa_split_floats_(size_t rows, int heads, int ldo, long nbatch, int nq, int cus);   // attention.hip
 
 // Every workspace address of a forward.  cus: the CU count of the device the attention launches plan their key split for.
 // pass: forward_impl's (a vcrnetIter pass with target reuse finds emb, d1, qc and kvc behind the plan).

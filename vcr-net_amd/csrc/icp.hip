@@ -10,8 +10,6 @@
 //   apply + converge  : s_i <- R s_i + t, batch-mean error from the partial sums in a fixed order
 #include "common.h"
 
-extern "C" int vcr_rigid_svd_f32(const vcr_rigid_svd_args* a, vcr_stream_t stream);
-
 namespace {
 
 struct IcpState { float prev_err; int stop; int iters; int pad; };

@@ -41,6 +41,7 @@
 // C == 4 : Cartesian xyz4 rows on the VALU: four lanes (one DPP quad) per query, 16 queries per wave, each lane
 //          scanning every fourth candidate (cross-lane: DPP quad_perm).
 #include "common.h"
+#include "vcr_internal.h"
 
 namespace {
 

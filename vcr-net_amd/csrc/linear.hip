@@ -10,6 +10,7 @@
 // makes the 16-lane b128 groups conflict-free.  Register-staged double buffering: the next
 // K-slab's global loads are issued before the MFMA block and written to the other LDS buffer after it.
 #include "common.h"
+#include "vcr_internal.h"
 #include <type_traits>
 #include <utility>
 

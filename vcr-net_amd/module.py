@@ -350,22 +350,27 @@ class VCRNet(nn.Module):
         # a replica's parameters are freed when its forward returns: what the cache keeps must own its memory
         g = (lambda k: sd[k].contiguous().clone()) if own else (lambda k: sd[k].contiguous())
         cw = native.VcrnetWeights()
+
+        def put(struct, field, key, tensor):
+            """The one way a packed tensor reaches cw: P[key] keeps the memory alive, struct.field is what the device reads."""
+            P[key] = tensor
+            setattr(struct, field, native.ptr(tensor))
+
+        def put_wb(struct, prefix, w, b, pair):                            # a (weight, bias) pair under P[prefix + field name]
+            put(struct, w, prefix + w, pair[0]); put(struct, b, prefix + b, pair[1])
+
         if self._emb_kind == "lpdnet":
-            P["c1_w"] = g("emb_nn.conv1_lpd.weight").view(64, 3).contiguous(); P["c1_b"] = g("emb_nn.conv1_lpd.bias")
-            P["c2_w"] = g("emb_nn.conv2_lpd.weight").view(64, 64).contiguous(); P["c2_b"] = g("emb_nn.conv2_lpd.bias")
-            w = g("emb_nn.convDG1.0.weight").view(128, 128)                # cat((neighbour, centre)): util.py:197
-            P["dg1_wpq"] = torch.cat((w[:, :64], w[:, 64:]), 0).contiguous()
-            P["dg1_bpq"] = torch.cat((torch.zeros_like(sd["emb_nn.convDG1.0.bias"]), sd["emb_nn.convDG1.0.bias"]))
-            P["dg2_w"] = g("emb_nn.convDG2.0.weight").view(128, 128).contiguous()
-            P["dg2_b"] = g("emb_nn.convDG2.0.bias")
-            w = g("emb_nn.convSN1.0.weight").view(256, 256)
-            P["sn1_wpq"] = torch.cat((w[:, :128], w[:, 128:]), 0).contiguous()
-            P["sn1_bpq"] = torch.cat((torch.zeros_like(sd["emb_nn.convSN1.0.bias"]), sd["emb_nn.convSN1.0.bias"]))
-            P["c3_w"] = g("emb_nn.conv3_lpd.weight").view(self.emb_dims, 512).contiguous()
-            P["c3_b"] = g("emb_nn.conv3_lpd.bias")
-            for k in ("c1_w", "c1_b", "c2_w", "c2_b", "dg1_wpq", "dg1_bpq", "dg2_w", "dg2_b", "sn1_wpq", "sn1_bpq",
-                      "c3_w", "c3_b"):
-                setattr(cw, k, native.ptr(P[k]))
+            conv = lambda name, *shape: (g(f"emb_nn.{name}.weight").view(*shape).contiguous(), g(f"emb_nn.{name}.bias"))
+
+            def halves(name, c):                                           # cat((neighbour, centre)): util.py:197
+                w, b = g(f"emb_nn.{name}.weight").view(2 * c, 2 * c), sd[f"emb_nn.{name}.bias"]
+                return torch.cat((w[:, :c], w[:, c:]), 0).contiguous(), torch.cat((torch.zeros_like(b), b))
+            put_wb(cw, "", "c1_w", "c1_b", conv("conv1_lpd", 64, 3))
+            put_wb(cw, "", "c2_w", "c2_b", conv("conv2_lpd", 64, 64))
+            put_wb(cw, "", "dg1_wpq", "dg1_bpq", halves("convDG1.0", 64))
+            put_wb(cw, "", "dg2_w", "dg2_b", conv("convDG2.0", 128, 128))
+            put_wb(cw, "", "sn1_wpq", "sn1_bpq", halves("convSN1.0", 128))
+            put_wb(cw, "", "c3_w", "c3_b", conv("conv3_lpd", self.emb_dims, 512))
         if self._emb_kind == "dgcnn":
             # eval-mode BatchNorm folded into the bias-free 1x1 convs (vcrnet_model.py:108-121); conv1 split into its
             # neighbour / centre halves (get_graph_feature concatenates (x_j, x_i), util.py:197), K padded 3 -> 32
@@ -377,52 +382,44 @@ class VCRNet(nn.Module):
             w1, b1 = fold(1)
             wpq = torch.zeros(128, 32, dtype=torch.float32, device=w1.device)
             wpq[:64, :3], wpq[64:, :3] = w1[:, :3], w1[:, 3:]
-            P["dg.c1_wpq"], P["dg.c1_bpq"] = wpq, torch.cat((torch.zeros_like(b1), b1)).contiguous()
+            put_wb(cw.dgcnn, "dg.", "c1_wpq", "c1_bpq", (wpq, torch.cat((torch.zeros_like(b1), b1)).contiguous()))
             for i in (2, 3, 4, 5):
-                P[f"dg.c{i}_w"], P[f"dg.c{i}_b"] = fold(i)
+                put_wb(cw.dgcnn, "dg.", f"c{i}_w", f"c{i}_b", fold(i))
             cw.emb_kind = 1
-            for f in ("c1_wpq", "c1_bpq", "c2_w", "c2_b", "c3_w", "c3_b", "c4_w", "c4_b", "c5_w", "c5_b"):
-                setattr(cw.dgcnn, f, native.ptr(P["dg." + f]))
         if self._emb_kind == "pointnet":
             # eval-mode BatchNorm1d folded into the bias-free pointwise convs (vcrnet_model.py:81-87)
             from .composed import _fold_bn
-            for i in (1, 2, 3, 4, 5):
-                P[f"pn.c{i}_w"], P[f"pn.c{i}_b"] = _fold_bn(sd, f"emb_nn.conv{i}", f"emb_nn.bn{i}")
+            for i in (1, 2, 3, 4, 5):                                      # conv1 / conv2: same shapes as LPDNet's stem
+                put_wb(cw if i < 3 else cw.pointnet, "pn.", f"c{i}_w", f"c{i}_b",
+                       _fold_bn(sd, f"emb_nn.conv{i}", f"emb_nn.bn{i}"))
             cw.emb_kind = 2
-            for i in (1, 2):                                               # same shapes as LPDNet's stem
-                setattr(cw, f"c{i}_w", native.ptr(P[f"pn.c{i}_w"])); setattr(cw, f"c{i}_b", native.ptr(P[f"pn.c{i}_b"]))
-            for f in ("c3_w", "c3_b", "c4_w", "c4_b", "c5_w", "c5_b"):
-                setattr(cw.pointnet, f, native.ptr(P["pn." + f]))
         if isinstance(self.pointer, _TransformerParams):
             pre = "pointer.model."
 
             def norm(field, name):
-                P[field + ".a"], P[field + ".b"] = g(name + ".a_2"), g(name + ".b_2")
-                setattr(cw, field, native.NormW(native.ptr(P[field + ".a"]), native.ptr(P[field + ".b"])))
+                put(getattr(cw, field), "ln_a", field + ".a", g(name + ".a_2"))
+                put(getattr(cw, field), "ln_b", field + ".b", g(name + ".b_2"))
 
             def mha(field, name, cross):
                 W = [g(f"{name}.linears.{i}.weight") for i in range(4)]
                 Bv = [g(f"{name}.linears.{i}.bias") for i in range(4)]
-                m = native.MhaW()
+                m = getattr(cw, field)
                 if cross:
-                    P[field + ".wq"], P[field + ".bq"] = W[0], Bv[0]
-                    P[field + ".wkv"] = torch.cat((W[1], W[2]), 0).contiguous()
-                    P[field + ".bkv"] = torch.cat((Bv[1], Bv[2])).contiguous()
-                    m.wq, m.bq = native.ptr(W[0]), native.ptr(Bv[0])
-                    m.wkv, m.bkv = native.ptr(P[field + ".wkv"]), native.ptr(P[field + ".bkv"])
+                    put_wb(m, field + ".", "wq", "bq", (W[0], Bv[0]))
+                    put_wb(m, field + ".", "wkv", "bkv",
+                           (torch.cat((W[1], W[2]), 0).contiguous(), torch.cat((Bv[1], Bv[2])).contiguous()))
                 else:
-                    P[field + ".wqkv"] = torch.cat(W[:3], 0).contiguous()
-                    P[field + ".bqkv"] = torch.cat(Bv[:3]).contiguous()
-                    m.wqkv, m.bqkv = native.ptr(P[field + ".wqkv"]), native.ptr(P[field + ".bqkv"])
-                P[field + ".wo"], P[field + ".bo"] = W[3], Bv[3]
-                m.wo, m.bo = native.ptr(W[3]), native.ptr(Bv[3])
-                setattr(cw, field, m)
+                    put_wb(m, field + ".", "wqkv", "bqkv", (torch.cat(W[:3], 0).contiguous(), torch.cat(Bv[:3]).contiguous()))
+                put_wb(m, field + ".", "wo", "bo", (W[3], Bv[3]))
 
             def ffn(field, name):
-                for leaf in ("w_1.weight", "w_1.bias", "w_2.weight", "w_2.bias"):
-                    P[field + "." + leaf] = g(name + "." + leaf)
-                setattr(cw, field, native.FfnW(*(native.ptr(P[field + "." + leaf]) for leaf in
-                                                 ("w_1.weight", "w_1.bias", "w_2.weight", "w_2.bias"))))
+                for f, leaf in (("w1", "w_1.weight"), ("b1", "w_1.bias"), ("w2", "w_2.weight"), ("b2", "w_2.bias")):
+                    put(getattr(cw, field), f, field + "." + leaf, g(name + "." + leaf))
+
+            def folded(site, f):                                           # f = (w, colsum, bias), also kept as one triple
+                P["fold." + site] = f
+                for field, t in zip(("w", "colsum", "bias"), f):
+                    put(getattr(cw, "fold_" + site), field, f"fold.{site}.{field}", t)
 
             e, d = pre + "encoder.layers.0", pre + "decoder.layers.0"
             norm("enc_ln0", e + ".sublayer.0.norm"); norm("enc_ln1", e + ".sublayer.1.norm")
@@ -441,16 +438,11 @@ class VCRNet(nn.Module):
                                      ("dec_cross_q", "dec_cross.wq", "dec_cross.bq", "dec_ln1"),
                                      ("dec_cross_kv", "dec_cross.wkv", "dec_cross.bkv", "enc_norm"),
                                      ("dec_ffn1", "dec_ffn.w_1.weight", "dec_ffn.w_1.bias", "dec_ln2")):
-                f = native.fold_layernorm(P[wk], P[bk], P[nk + ".a"], P[nk + ".b"])
-                P["fold." + site] = f
-                P["fold." + site + ".w"] = f[0]
-                setattr(cw, "fold_" + site, native.FoldedW(*(native.ptr(t) for t in f)))
+                folded(site, native.fold_layernorm(P[wk], P[bk], P[nk + ".a"], P[nk + ".b"]))
             if self.merge_encdec:
                 # the encoder's and the decoder's first sublayers both read the embedding rows: one stacked projection
-                f = tuple(torch.cat((a_, b_), 0).contiguous() for a_, b_ in zip(P["fold.enc_qkv"], P["fold.dec_qkv"]))
-                P["fold.encdec_qkv"] = f
-                P["fold.encdec_qkv.w"] = f[0]
-                cw.fold_encdec_qkv = native.FoldedW(*(native.ptr(t) for t in f))
+                folded("encdec_qkv", tuple(torch.cat((a_, b_), 0).contiguous()
+                                           for a_, b_ in zip(P["fold.enc_qkv"], P["fold.dec_qkv"])))
         else:
             cw.has_pointer = 2 if isinstance(self.pointer, _Identity) else 0
         if self.linear_mode not in LINEAR_MODES:
@@ -469,14 +461,13 @@ class VCRNet(nn.Module):
             #  device drain -- on every forward: 0.63 ms of a 4.0 ms step, profiles/r6a_split_trace_gaps.json)
             for site, name in src.items():
                 if name in P:
-                    P["split." + site] = native.split_bf16x3(P[name])
-                    setattr(cw.split, site, native.ptr(P["split." + site]))
+                    put(cw.split, site, "split." + site, native.split_bf16x3(P[name]))
         cw.E, cw.F, cw.heads, cw.k = self.emb_dims, self._ff, self._n_heads, int(self.emb_nn.k)
         cw.head_mode = {"topK": 0, "dist": 1, "att": 2}[self._vcp]
         if self._vcp == "att":
             for i in (0, 1):
-                P[f"att.w{i}"], P[f"att.b{i}"] = g(f"head.linears_emb.{i}.weight"), g(f"head.linears_emb.{i}.bias")
-                setattr(cw, f"att_w{i}", native.ptr(P[f"att.w{i}"])); setattr(cw, f"att_b{i}", native.ptr(P[f"att.b{i}"]))
+                put(cw, f"att_w{i}", f"att.w{i}", g(f"head.linears_emb.{i}.weight"))
+                put(cw, f"att_b{i}", f"att.b{i}", g(f"head.linears_emb.{i}.bias"))
         cw.cycle = int(bool(self.cycle))
         cw.linear_mfma, cw.linear_bk, cw.linear_bm = int(self.linear_mfma), int(self.linear_bk), int(self.linear_bm)
         cw.knn_waves = int(self.knn_waves)
@@ -502,9 +493,7 @@ class VCRNet(nn.Module):
             for k_ in [k_ for k_ in sh.pool if k_[2] == device and k_ != key]:     # keep one shape resident per device
                 for b_ in sh.pool.pop(k_):
                     self._retire(b_)
-        L = native.lib()
-        L.vcr_vcrnet_iter_workspace_bytes.restype = C.c_size_t
-        nbytes = L.vcr_vcrnet_iter_workspace_bytes(C.byref(self._cw), B, N, int(iters))
+        nbytes = native.lib().vcr_vcrnet_iter_workspace_bytes(C.byref(self._cw), B, N, int(iters))
         return key, {"ws": torch.empty(nbytes + 256, dtype=torch.uint8, device=device)}
 
     MAX_IDLE_WORKSPACES = 4                                # per shape: more concurrent calls than this allocate and free

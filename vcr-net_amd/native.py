@@ -227,20 +227,102 @@ class Trace(C.Structure):
                 ("names", C.c_char_p * VCR_TRACE_MAX)]
 
 
-_SIGS = {
-    "vcr_pointwise_f32": PointwiseArgs, "vcr_knn_f32": KnnArgs, "vcr_linear_f32": LinearArgs,
-    "vcr_layernorm_f32": LayerNormArgs, "vcr_rowside_f32": RowsideArgs, "vcr_edgeconv_f32": EdgeconvArgs, "vcr_edgeconv_bf16x3_f32": EdgeconvArgs,
-    "vcr_gathermax_f32": GathermaxArgs, "vcr_sdpa_f32": SdpaArgs, "vcr_sdpa_bf16x3_f32": SdpaArgs, "vcr_softcorr_f32": SoftcorrArgs,
-    "vcr_rigid_svd_f32": RigidSvdArgs, "vcr_pairscore_f32": PairscoreArgs, "vcr_rankselect_f32": RankselectArgs,
-    "vcr_gather_rows_f32": GatherArgs, "vcr_scoremass_f32": ScoremassArgs, "vcr_keymass_f32": KeymassArgs, "vcr_make_pairs_f32": MakePairsArgs,
-    "vcr_edgerows_f32": EdgerowsArgs, "vcr_segmax_f32": SegmaxArgs, "vcr_edgechain_f32": EdgechainArgs,
-    "vcr_fps_f32": FpsArgs,
+class IcpArgs(C.Structure):
+    _fields_ = [("src4", f32p), ("dst4", f32p), ("B", C.c_int), ("N", C.c_int), ("M", C.c_int),
+                ("max_iterations", C.c_int), ("tolerance", C.c_float), ("final4", f32p), ("R", f32p), ("t", f32p),
+                ("R_ba", f32p), ("t_ba", f32p), ("iterations", f32p)]
+
+
+class PoseStepArgs(C.Structure):
+    _fields_ = [("R_i", f32p), ("t_i", f32p), ("B", C.c_int), ("N", C.c_int), ("in_cf", f32p), ("out_cf", f32p),
+                ("compose", C.c_int), ("R_f", f32p), ("t_f", f32p), ("R_ba", f32p), ("t_ba", f32p)]
+
+
+# ---- the boundary in one place: every C struct's mirror, every exported function's signature --------------------------
+# tests/test_abi.py holds both maps to the headers: STRUCTS to gcc's sizeof / offsetof of include/vcr_hip.h, SIGNATURES to the
+# prototypes of include/vcr_hip.h (PUBLIC) and csrc/vcr_internal.h (INTERNAL).  lib() applies SIGNATURES once, under the load:
+# nothing else in the package, the tests or the profile tools assigns an argtypes / restype.
+
+STRUCTS = {
+    "vcr_pointwise_args": PointwiseArgs, "vcr_knn_args": KnnArgs, "vcr_knn_order_args": KnnOrderArgs, "vcr_fps_args": FpsArgs,
+    "vcr_linear_args": LinearArgs, "vcr_layernorm_args": LayerNormArgs, "vcr_rowside_args": RowsideArgs,
+    "vcr_edgeconv_args": EdgeconvArgs, "vcr_gathermax_args": GathermaxArgs, "vcr_edgerows_args": EdgerowsArgs,
+    "vcr_edgechain_args": EdgechainArgs, "vcr_segmax_args": SegmaxArgs, "vcr_sdpa_args": SdpaArgs,
+    "vcr_keymass_args": KeymassArgs, "vcr_softcorr_args": SoftcorrArgs, "vcr_pairscore_args": PairscoreArgs,
+    "vcr_scoremass_args": ScoremassArgs, "vcr_rankselect_args": RankselectArgs, "vcr_gather_args": GatherArgs,
+    "vcr_rigid_svd_args": RigidSvdArgs, "vcr_icp_args": IcpArgs, "vcr_make_pairs_args": MakePairsArgs,
+    "vcr_pose_step_args": PoseStepArgs, "vcr_vcrnet_weights": VcrnetWeights, "vcr_vcrnet_io": VcrnetIo, "vcr_trace": Trace,
 }
+
+_int, _size, _long, _float, _vp = C.c_int, C.c_size_t, C.c_long, C.c_float, C.c_void_p    # (_vp: device pointers, void*, streams)
+_P = C.POINTER
+_intp = _P(C.c_int)
+
+# int f(const vcr_X_args*, vcr_stream_t): one launch (or a few) described by one struct
+_ARGS_STREAM = {
+    "vcr_pointwise_f32": PointwiseArgs, "vcr_knn_f32": KnnArgs, "vcr_knn_order_f32": KnnOrderArgs, "vcr_linear_f32": LinearArgs,
+    "vcr_layernorm_f32": LayerNormArgs, "vcr_rowside_f32": RowsideArgs, "vcr_edgeconv_f32": EdgeconvArgs,
+    "vcr_edgeconv_bf16x3_f32": EdgeconvArgs, "vcr_gathermax_f32": GathermaxArgs, "vcr_sdpa_f32": SdpaArgs,
+    "vcr_sdpa_bf16x3_f32": SdpaArgs, "vcr_softcorr_f32": SoftcorrArgs, "vcr_rigid_svd_f32": RigidSvdArgs,
+    "vcr_pairscore_f32": PairscoreArgs, "vcr_rankselect_f32": RankselectArgs, "vcr_gather_rows_f32": GatherArgs,
+    "vcr_scoremass_f32": ScoremassArgs, "vcr_keymass_f32": KeymassArgs, "vcr_make_pairs_f32": MakePairsArgs,
+    "vcr_edgerows_f32": EdgerowsArgs, "vcr_segmax_f32": SegmaxArgs, "vcr_edgechain_f32": EdgechainArgs, "vcr_fps_f32": FpsArgs,
+    "vcr_pose_step_f32": PoseStepArgs,
+}
+
+# name -> (restype, [argtypes]): the 51 prototypes of include/vcr_hip.h
+PUBLIC = {name: (_int, [_P(st), _vp]) for name, st in _ARGS_STREAM.items()}
+PUBLIC.update({
+    "vcr_strerror": (C.c_char_p, [_int]),
+    "vcr_abi_version": (_int, []),
+    "vcr_rows4_f32": (_int, [_vp, _vp, _int, _int, _vp]),
+    "vcr_rows4_pq_f32": (_int, [_vp, _vp, _int, _int, _vp, _int, _vp, _int, _vp, _int, _vp]),
+    "vcr_knn_tie_work_bytes": (_size, [_int]),
+    "vcr_knn_tie_slot_bytes": (_size, [_int, _int]),
+    "vcr_knn_ties_inline": (_int, [_P(KnnArgs)]),
+    "vcr_knn_ties_f32": (_int, [_P(KnnArgs), _P(KnnArgs), _vp]),
+    "vcr_knn_pair_f32": (_int, [_P(KnnArgs), _P(KnnArgs), _vp]),
+    "vcr_linear_config": (_int, [_P(LinearArgs)]),
+    "vcr_linear_pair_f32": (_int, [_P(LinearArgs), _P(LinearArgs), _vp]),
+    "vcr_fold_layernorm_f32": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp]),
+    "vcr_split_bf16x3_f32": (_int, [_vp, _vp, _size, _vp]),
+    "vcr_linear_bf16x3_f32": (_int, [_P(LinearArgs), _vp, _vp]),
+    "vcr_icp_workspace_bytes": (_size, [_int, _int]),
+    "vcr_icp_f32": (_int, [_P(IcpArgs), _vp, _size, _vp]),
+    "vcr_fps_form": (_int, [_P(FpsArgs), _intp, _intp]),
+    "vcr_vcrnet_workspace_bytes": (_size, [_P(VcrnetWeights), _int, _int]),
+    "vcr_vcrnet_iter_workspace_bytes": (_size, [_P(VcrnetWeights), _int, _int, _int]),
+    "vcr_vcrnet_pairs": (_int, [_P(VcrnetWeights), _int]),
+    "vcr_vcrnet_forward_f32": (_int, [_P(VcrnetWeights), _P(VcrnetIo), _vp, _size, _vp]),
+    "vcr_vcrnet_forward_traced_f32": (_int, [_P(VcrnetWeights), _P(VcrnetIo), _vp, _size, _vp, _P(Trace)]),
+    "vcr_vcrnet_iter_f32": (_int, [_P(VcrnetWeights), _P(VcrnetIo), _int, _vp, _size, _vp, _P(Trace)]),
+    "vcr_event_create": (_int, [_P(_vp)]),
+    "vcr_event_destroy": (_int, [_vp]),
+    "vcr_event_record": (_int, [_vp, _vp]),
+    "vcr_event_elapsed_ms": (_int, [_vp, _vp, _P(_float)]),
+})
+
+# the library-internal planner reporters of csrc/vcr_internal.h (host only; tests and profile tools call them)
+INTERNAL = {
+    "vcr_linear_forms_": (_int, [_P(LinearArgs), _P(LinearArgs), _intp, _intp, _intp]),
+    "vcr_knn_forms_": (_int, [_P(KnnArgs), _P(KnnArgs), _intp, _intp, _intp]),
+    "vcr_sdpa_forms_": (_int, [_P(SdpaArgs), _intp, _intp]),
+    "vcr_sdpa_split_floats_": (_long, [_size, _int, _int, _long, _int, _int]),
+    "vcr_edgeconv_forms_": (_int, [_P(EdgeconvArgs), _int, _intp, _intp]),
+    "vcr_gathermax_forms_": (_int, [_P(GathermaxArgs), _intp, _intp, _intp, _intp]),
+}
+
+SIGNATURES = {**PUBLIC, **INTERNAL}
+
+# int vcr_dbg_probe_<stem>(void* host_dst, int clear): the buffer readers of an instrumented build (profiles/experiments/probes.h)
+# that profiles/timeline_*.py load through LIB_PATH; typed where the loaded library exports them
+PROBES = {"vcr_dbg_probe_" + stem: (_int, [_vp, _int])
+          for stem in ("linear", "linear_bf16x3", "attention", "attention_bf16x3", "knn", "pointwise", "edgeconv")}
 
 _lib: Optional[C.CDLL] = None
 
 
-ABI_VERSION = 27         # include/vcr_hip.h vcr_abi_version(); the ctypes structs below mirror that header
+ABI_VERSION = 27         # include/vcr_hip.h vcr_abi_version(); the ctypes structs above mirror that header
 
 
 class VcrHipError(RuntimeError):
@@ -248,43 +330,20 @@ class VcrHipError(RuntimeError):
 
 
 def lib() -> C.CDLL:
-    """Load libvcr_hip.so (once).  Raises if it has not been built -- there is no CPU fallback."""
+    """Load libvcr_hip.so (once) and type every entry point from SIGNATURES.  Raises if it has not been built -- there is no
+    CPU fallback."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise VcrHipError(f"{LIB_PATH} not built: run `python vcr-net_amd/build.py` "
                               "(or __graft_entry__.build()); the HIP path has no fallback")
         L = C.CDLL(LIB_PATH)
-        for name, st in _SIGS.items():
+        for name, (res, args) in list(SIGNATURES.items()) + [(n, s) for n, s in PROBES.items() if hasattr(L, n)]:
             fn = getattr(L, name)
-            fn.argtypes = [C.POINTER(st), C.c_void_p]
-            fn.restype = C.c_int
-        L.vcr_strerror.argtypes = [C.c_int]; L.vcr_strerror.restype = C.c_char_p
-        L.vcr_abi_version.restype = C.c_int
+            fn.restype, fn.argtypes = res, args
         if L.vcr_abi_version() != ABI_VERSION:
             raise VcrHipError(f"{LIB_PATH} exports ABI {L.vcr_abi_version()}, these bindings are for {ABI_VERSION}: "
                               "rebuild with `python vcr-net_amd/build.py`")
-        L.vcr_vcrnet_workspace_bytes.argtypes = [C.POINTER(VcrnetWeights), C.c_int, C.c_int]
-        L.vcr_vcrnet_workspace_bytes.restype = C.c_size_t
-        L.vcr_vcrnet_iter_workspace_bytes.argtypes = [C.POINTER(VcrnetWeights), C.c_int, C.c_int, C.c_int]
-        L.vcr_vcrnet_iter_workspace_bytes.restype = C.c_size_t
-        L.vcr_vcrnet_forward_f32.argtypes = [C.POINTER(VcrnetWeights), C.POINTER(VcrnetIo), C.c_void_p, C.c_size_t,
-                                             C.c_void_p]
-        L.vcr_vcrnet_forward_f32.restype = C.c_int
-        L.vcr_vcrnet_forward_traced_f32.argtypes = [C.POINTER(VcrnetWeights), C.POINTER(VcrnetIo), C.c_void_p,
-                                                    C.c_size_t, C.c_void_p, C.POINTER(Trace)]
-        L.vcr_vcrnet_forward_traced_f32.restype = C.c_int
-        L.vcr_vcrnet_pairs.argtypes = [C.POINTER(VcrnetWeights), C.c_int]; L.vcr_vcrnet_pairs.restype = C.c_int
-        L.vcr_vcrnet_iter_f32.argtypes = [C.POINTER(VcrnetWeights), C.POINTER(VcrnetIo), C.c_int, C.c_void_p,
-                                          C.c_size_t, C.c_void_p, C.POINTER(Trace)]
-        L.vcr_vcrnet_iter_f32.restype = C.c_int
-        L.vcr_fps_form.argtypes = [C.POINTER(FpsArgs), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.vcr_fps_form.restype = C.c_int
-        L.vcr_event_create.argtypes = [C.POINTER(C.c_void_p)]; L.vcr_event_create.restype = C.c_int
-        L.vcr_event_destroy.argtypes = [C.c_void_p]; L.vcr_event_destroy.restype = C.c_int
-        L.vcr_event_record.argtypes = [C.c_void_p, C.c_void_p]; L.vcr_event_record.restype = C.c_int
-        L.vcr_event_elapsed_ms.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
-        L.vcr_event_elapsed_ms.restype = C.c_int
         _lib = L
     return _lib
 
@@ -357,8 +416,10 @@ def same_device(*tensors) -> torch.device:
     return next(iter(devs))
 
 
-def call(name: str, args: C.Structure) -> None:
-    check(getattr(lib(), name)(C.byref(args), C.c_void_p(stream_ptr())), name)
+def call(name: str, *args) -> None:
+    """Enqueue the entry point `name` on the current stream: its arguments as SIGNATURES types them (an args struct goes by
+    reference), then the stream; a return code other than 0 raises."""
+    check(getattr(lib(), name)(*args, stream_ptr()), name)
 
 
 def _guarded(fn):
@@ -428,8 +489,6 @@ def _tie_work(a, N, device, keep, slots_for=0):
     """Long rows (vcr_knn_tie_work_bytes(N) > 0, N > ~10 100): the replay's global scratch (knn(), knn_pair()).
     slots_for = B: vcr_knn_tie_slot_bytes(B, N) instead -- the launch replays its own ties (vcr_knn_args.tie_inline 2)."""
     L = lib()
-    L.vcr_knn_tie_work_bytes.restype, L.vcr_knn_tie_work_bytes.argtypes = C.c_size_t, [C.c_int]
-    L.vcr_knn_tie_slot_bytes.restype, L.vcr_knn_tie_slot_bytes.argtypes = C.c_size_t, [C.c_int, C.c_int]
     need = L.vcr_knn_tie_slot_bytes(slots_for, N) if slots_for else L.vcr_knn_tie_work_bytes(N)
     if need:
         work = torch.empty(need, dtype=torch.uint8, device=device)
@@ -443,7 +502,6 @@ def knn_pair(feat, sq, xyz4, k, xt=None, order=None, tie_slots=False, prefill=No
     -> (idx_feat, idx_xyz), tie replay included.  order = knn_order()'s dict: the ordered search (vcr_knn_args.perm).
     tie_slots: per-workgroup replay slots (vcr_knn_tie_slot_bytes) -- tied rows are replayed inside the launch.
     prefill: as for knn()."""
-    L = lib()
     out, args, keep = [], [], []
     for x, s_ in ((feat, sq), (xyz4, None)):
         B, N, Cc = x.shape
@@ -461,16 +519,13 @@ def knn_pair(feat, sq, xyz4, k, xt=None, order=None, tie_slots=False, prefill=No
         a.ord_ok = ptr(order.get("ord_ok"))
         a = args[1]
         a.xp, a.cen, a.cen_rad, a.cen_sqmax = o("xyz4_p"), o("cen4"), o("cen4_rad"), o("cen4_sqmax")
-    L.vcr_knn_pair_f32.argtypes = [C.POINTER(KnnArgs), C.POINTER(KnnArgs), C.c_void_p]
-    L.vcr_knn_pair_f32.restype = C.c_int
-    check(L.vcr_knn_pair_f32(C.byref(args[0]), C.byref(args[1]), C.c_void_p(stream_ptr())), "vcr_knn_pair_f32")
+    call("vcr_knn_pair_f32", args[0], args[1])
     return out[0], out[1]
 
 
 @_guarded
 def knn_pair_deferred(xa, sqa, xb, sqb, k, prefill=None):
     """Two kNN launches with tie_defer and ONE vcr_knn_ties_f32 replay for both (the LPDNet pattern) -> (idx_a, idx_b)."""
-    L = lib()
     args, keep = [], []
     for x, sq in ((xa, sqa), (xb, sqb)):
         B, N, Cc = x.shape
@@ -482,9 +537,7 @@ def knn_pair_deferred(xa, sqa, xb, sqb, k, prefill=None):
         _tie_work(a, N, x.device, work)
         call("vcr_knn_f32", a)
         args.append(a); keep.append((idx, ties, work))
-    L.vcr_knn_ties_f32.argtypes = [C.POINTER(KnnArgs), C.POINTER(KnnArgs), C.c_void_p]
-    L.vcr_knn_ties_f32.restype = C.c_int
-    check(L.vcr_knn_ties_f32(C.byref(args[0]), C.byref(args[1]), C.c_void_p(stream_ptr())), "vcr_knn_ties_f32")
+    call("vcr_knn_ties_f32", args[0], args[1])
     return keep[0][0], keep[1][0]
 
 
@@ -514,33 +567,25 @@ def linear(x, w, bias=None, relu=False, residual=None, out=None, ln=None, want_s
 @_guarded
 def fold_layernorm(w, bias, ln_a, ln_b):
     """vcr_fold_layernorm_f32: (w * a, colsum, bias + w b) for a Linear that consumes LayerNorm(a, b)."""
-    L = lib()
     N, K = w.shape
     w = w.contiguous()
     wf, cs, bf = _f32(N, K, device=w.device), _f32(N, device=w.device), _f32(N, device=w.device)
-    L.vcr_fold_layernorm_f32.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4
-    L.vcr_fold_layernorm_f32.restype = C.c_int
-    check(L.vcr_fold_layernorm_f32(ptr(w), ptr(bias), ptr(ln_a), ptr(ln_b), N, K, ptr(wf), ptr(cs), ptr(bf),
-                                   C.c_void_p(stream_ptr())), "vcr_fold_layernorm_f32")
+    call("vcr_fold_layernorm_f32", ptr(w), ptr(bias), ptr(ln_a), ptr(ln_b), N, K, ptr(wf), ptr(cs), ptr(bf))
     return wf, cs, bf
 
 
 @_guarded
 def split_bf16x3(w):
     """fp32 tensor -> int16 [3, numel] bf16 planes (hi, mid, lo) with hi + mid + lo == w exactly."""
-    L = lib()
     w = w.contiguous().float()
     planes = torch.empty(3, w.numel(), dtype=torch.int16, device=w.device)
-    L.vcr_split_bf16x3_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.vcr_split_bf16x3_f32.restype = C.c_int
-    check(L.vcr_split_bf16x3_f32(ptr(w), ptr(planes), w.numel(), C.c_void_p(stream_ptr())), "vcr_split_bf16x3_f32")
+    call("vcr_split_bf16x3_f32", ptr(w), ptr(planes), w.numel())
     return planes
 
 
 @_guarded
 def linear_bf16x3(x, w_planes, n_out, bias=None, relu=False, residual=None, out=None, ln=None, want_stats=False):
     """vcr_linear_bf16x3_f32; ln / want_stats as in linear() (w_planes = split_bf16x3 of the folded weight)."""
-    L = lib()
     M, K = x.shape
     y = out if out is not None else _f32(M, n_out, device=x.device)
     stats = _f32(M, n_out // 64, 2, device=x.device) if want_stats else None
@@ -549,9 +594,7 @@ def linear_bf16x3(x, w_planes, n_out, bias=None, relu=False, residual=None, out=
     if ln is not None:
         a.ln_stats_in, a.ln_nseg, a.ln_colsum, a.ln_eps = ptr(ln[0]), ln[0].shape[1], ptr(ln[1]), ln[2]
     a.stats_out = ptr(stats)
-    L.vcr_linear_bf16x3_f32.argtypes = [C.POINTER(LinearArgs), C.c_void_p, C.c_void_p]
-    L.vcr_linear_bf16x3_f32.restype = C.c_int
-    check(L.vcr_linear_bf16x3_f32(C.byref(a), ptr(w_planes), C.c_void_p(stream_ptr())), "vcr_linear_bf16x3_f32")
+    call("vcr_linear_bf16x3_f32", a, ptr(w_planes))
     return (y, stats) if want_stats else y
 
 
@@ -773,44 +816,30 @@ def farthest_point_sample(xyz, npoint):
     return fps(xyz.float(), npoint, want_points=False)[0].long()
 
 
-class IcpArgs(C.Structure):
-    _fields_ = [("src4", f32p), ("dst4", f32p), ("B", C.c_int), ("N", C.c_int), ("M", C.c_int),
-                ("max_iterations", C.c_int), ("tolerance", C.c_float), ("final4", f32p), ("R", f32p), ("t", f32p),
-                ("R_ba", f32p), ("t_ba", f32p), ("iterations", f32p)]
-
-
 @_guarded
 def to_rows4(x_cf):
     """[B,3,N] channels-first points -> [B,N,4] rows (x, y, z, |p|^2) (layout plumbing for the C-ABI)."""
-    L = lib()
     B, _, N = x_cf.shape
     x = x_cf.contiguous().float()
     out = _f32(B, N, 4, device=x.device)
-    L.vcr_rows4_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]; L.vcr_rows4_f32.restype = C.c_int
-    check(L.vcr_rows4_f32(ptr(x), ptr(out), B, N, C.c_void_p(stream_ptr())), "vcr_rows4_f32")
+    call("vcr_rows4_f32", ptr(x), ptr(out), B, N)
     return out
 
 
 @_guarded
 def rows4_pq(x_cf, wpq, bpq):
     """vcr_rows4_pq_f32: [B,3,N] -> ([B,N,4] rows, [B*N, C] = W xyz + b with W [C, >= 3])."""
-    L = lib()
     B, _, N = x_cf.shape
     x = x_cf.contiguous().float()
     Cc = wpq.shape[0]
     out, pq = _f32(B, N, 4, device=x.device), _f32(B * N, Cc, device=x.device)
-    L.vcr_rows4_pq_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
-                                   C.c_void_p, C.c_int, C.c_void_p]
-    L.vcr_rows4_pq_f32.restype = C.c_int
-    check(L.vcr_rows4_pq_f32(ptr(x), ptr(out), B, N, ptr(wpq), wpq.stride(0), ptr(bpq), Cc, ptr(pq), Cc,
-                             C.c_void_p(stream_ptr())), "vcr_rows4_pq_f32")
+    call("vcr_rows4_pq_f32", ptr(x), ptr(out), B, N, ptr(wpq), wpq.stride(0), ptr(bpq), Cc, ptr(pq), Cc)
     return out, pq
 
 
 @_guarded
 def icp(src_cf, dst_cf, max_iterations=10, tolerance=0.001):
     """ICP.forward (model/icp_model.py:26-48) on the device: returns (final [B,3,N], R, t, R_ba, t_ba, iters)."""
-    L = lib()
     B, _, N = src_cf.shape
     M = dst_cf.shape[2]
     dev = src_cf.device
@@ -818,20 +847,13 @@ def icp(src_cf, dst_cf, max_iterations=10, tolerance=0.001):
     final4 = _f32(B, N, 4, device=dev)
     R, t, Rb, tb = _f32(B, 3, 3, device=dev), _f32(B, 3, device=dev), _f32(B, 3, 3, device=dev), _f32(B, 3, device=dev)
     iters = torch.zeros(1, dtype=torch.int32, device=dev)
-    L.vcr_icp_workspace_bytes.argtypes = [C.c_int, C.c_int]; L.vcr_icp_workspace_bytes.restype = C.c_size_t
-    L.vcr_icp_f32.argtypes = [C.POINTER(IcpArgs), C.c_void_p, C.c_size_t, C.c_void_p]; L.vcr_icp_f32.restype = C.c_int
-    nbytes = L.vcr_icp_workspace_bytes(B, N)
+    nbytes = lib().vcr_icp_workspace_bytes(B, N)
     ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
     off = (-ws.data_ptr()) % 256
     a = IcpArgs(ptr(src4), ptr(dst4), B, N, M, max_iterations, tolerance, ptr(final4), ptr(R), ptr(t), ptr(Rb),
                 ptr(tb), ptr(iters))
-    check(L.vcr_icp_f32(C.byref(a), C.c_void_p(ws.data_ptr() + off), nbytes, C.c_void_p(stream_ptr())), "vcr_icp_f32")
+    call("vcr_icp_f32", a, ws.data_ptr() + off, nbytes)
     return final4[:, :, :3].transpose(1, 2).contiguous(), R, t, Rb, tb, iters
-
-
-class PoseStepArgs(C.Structure):
-    _fields_ = [("R_i", f32p), ("t_i", f32p), ("B", C.c_int), ("N", C.c_int), ("in_cf", f32p), ("out_cf", f32p),
-                ("compose", C.c_int), ("R_f", f32p), ("t_f", f32p), ("R_ba", f32p), ("t_ba", f32p)]
 
 
 @_guarded
