@@ -57,6 +57,8 @@ __device__ __forceinline__ double quad_get(double v, int lane_in_quad) {   // la
 
 // One-sided Jacobi sweeps on the quad: lane i < 3 holds a[0..2] = row i of A (initially H) and v[0..2] = row i of V
 // (initially I); lane 3 holds zeros.  The control flow is uniform over the quad (the inner products are quad sums).
+// Every test is relative to the columns' own norms: H scales with the square of the cloud size (ga with its fourth power),
+// and a cloud of any size the fp32 inputs can hold must converge like a unit one.
 __device__ __forceinline__ void jacobi_sweeps_quad(double (&a)[3], double (&v)[3]) {
   for (int sweep = 0; sweep < 40; ++sweep) {
     double off = 0.0;
@@ -64,8 +66,9 @@ __device__ __forceinline__ void jacobi_sweeps_quad(double (&a)[3], double (&v)[3
     for (int pq = 0; pq < 3; ++pq) {
       const int p = (pq == 2) ? 1 : 0, q = (pq == 0) ? 1 : 2;
       const double al = quad_sum(a[p] * a[p]), be = quad_sum(a[q] * a[q]), ga = quad_sum(a[p] * a[q]);
-      if (fabs(ga) <= 1e-30 + 1e-17 * sqrt(al * be)) continue;
-      off = fmax(off, fabs(ga) / sqrt(al * be + 1e-300));
+      const double ab = sqrt(al) * sqrt(be);                // (not sqrt(al * be): the product can leave fp64's range)
+      if (!(fabs(ga) > 1e-17 * ab)) continue;               // orthogonal already; a zero column (ab == 0) is skipped too
+      off = fmax(off, fabs(ga) / ab);
       const double zeta = (be - al) / (2.0 * ga);
       const double tt = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
       const double c = 1.0 / sqrt(1.0 + tt * tt), s = c * tt;
@@ -98,7 +101,7 @@ __device__ void svd3_finish(const double A[3][3], const double V[3][3], double R
   // vcrnetIter passes): R is not unique -- LAPACK's choice in the reference is arbitrary too -- we take the
   // completion closest to the coordinate axes, and R = I for H = 0.
   const double s0 = sig[ord[0]];
-  if (!(s0 > 1e-300)) {
+  if (!(s0 > 0)) {
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) U[i][j] = W[i][j];
   } else {
     if (sig[ord[1]] <= 1e-12 * s0) {
