@@ -8,7 +8,7 @@ The kept SET is therefore an artefact of introselect's pivoting / the heap's sha
 returned in -- which matters once: the reference's ``knn`` (util/util.py:159) drops the entry ``topk`` returns FIRST, so
 when the best value of a row is shared (copies of a point; a neighbour whose distance rounds to the point's own) WHICH of the
 tied entries is dropped comes out of that sort.  The HIP kNN kernels replay both for rows with such a tie
-(vcr-net_amd/csrc/knn.hip, knn_tiebreak_kernel / tiebreak_row).  This module restates the libstdc++ algorithms
+(vcr-net_amd/csrc/knn_tiebreak.h, knn_tiebreak_kernel / tiebreak_row).  This module restates the libstdc++ algorithms
 (bits/stl_algo.h: __introselect, __unguarded_partition_pivot, __move_median_to_first, __insertion_sort;
 __introsort_loop, __final_insertion_sort; bits/stl_heap.h: __make_heap, __adjust_heap, __push_heap, __pop_heap,
 __heap_select, __sort_heap) in plain Python;

@@ -124,6 +124,28 @@ def test_knn_feature_space(nat, W, N, k):
     assert nbad <= max(2, h.shape[0] * N // 100)
 
 
+@pytest.mark.parametrize("N,k", [(17, 5),      # two tiles of 16, the second ragged
+                                 (33, 5),      # three tiles: the step's second tile does not exist (tile + 1 < ntiles)
+                                 (48, 20)])    # three full tiles
+def test_knn_16_query_scan_at_a_few_tiles(nat, W, N, k):
+    """The 16-query body's two-tile step at the smallest clouds, both of its operand forms: the feature-space search forced onto
+    knn64c_kernel (waves=8) against the 32-query kernel (waves=1), and the Cartesian search unsplit (waves=1: knn3c_kernel) against
+    the form a grid this small takes by itself (four waves per query group on the VALU).  Ties are replayed in every form, so
+    the sets are equal."""
+    g = golden("whole_n1024_b2")
+    x3 = torch.from_numpy(g["src"][:, :, :N])
+    h = F.relu(F.conv1d(x3, W["emb_nn.conv1_lpd.weight"], W["emb_nn.conv1_lpd.bias"]))
+    h = F.relu(F.conv1d(h, W["emb_nn.conv2_lpd.weight"], W["emb_nn.conv2_lpd.bias"]))
+    feat = dev(h.transpose(1, 2))
+    sq = dev((h ** 2).sum(1))
+    assert x3.shape[0] == 2
+    i16, i32 = nat.knn(feat, sq, k, waves=8), nat.knn(feat, sq, k, waves=1)
+    assert torch.equal(torch.sort(i16, -1).values, torch.sort(i32, -1).values)
+    xyz4 = dev(torch.cat((x3.transpose(1, 2), (x3 ** 2).sum(1).unsqueeze(-1)), -1))
+    i3c, i3 = nat.knn(xyz4, None, k, waves=1), nat.knn(xyz4, None, k)
+    assert torch.equal(torch.sort(i3c, -1).values, torch.sort(i3, -1).values)
+
+
 @pytest.mark.parametrize("N,k", [(256, 20), (1024, 20), (768, 20), (100, 20), (512, 40), (2048, 20), (4096, 40), (21, 20),
                                  (45, 40), (1000, 5), (1024, 50), (4096, 62), (63, 62)])
 def test_knn_cartesian(nat, N, k):
@@ -878,6 +900,39 @@ def test_knn_ordered_search_keeps_the_sets(nat, B, N, k, kind):
     pair launch: the same neighbour SET on every row -- smooth features (a function of the coordinates, as the stem's are),
     features unrelated to the coordinates (nothing can be skipped), every point twice (the rank-0 rule picks by point index),
     lattices (thousands of exact ties: the replay) and a cloud of one repeated point."""
+    _ordered_search_keeps_the_sets(nat, B, N, k, kind)
+
+
+@pytest.mark.parametrize("kind", ["smooth", "lattice"])
+@pytest.mark.parametrize("B,N,k", [(114, 144, 20),    # 9 tiles: the whole cloud is the near range, odd sequence length
+                                   (103, 160, 20),    # 10 tiles: one tile outside the near range -- a second sequence of <= 1 tile
+                                   (64, 250, 20), (64, 250, 40),   # ragged last tile (250 = 15 * 16 + 10), both list sizes
+                                   (52, 330, 20)])    # 21 tiles, ragged, near range clipped at either end for different waves
+def test_knn_ordered_search_keeps_the_sets_over_a_handful_of_tiles(nat, B, N, k, kind):
+    """The same comparison where the two-tile step of the ordered scan meets its edges: sequences of one tile, of an odd number of
+    tiles, a ragged last tile.  Every case has >= 1024 groups of 16 queries per search, so that the pair takes the fused form that
+    reads the ordered inputs -- asserted through vcr_knn_forms_, not assumed."""
+    _ordered_search_keeps_the_sets(nat, B, N, k, kind, must_be_ordered=True)
+
+
+def _pair_takes_the_ordered_form(nat, feat, sq, x4, ft, k):
+    """vcr_knn_forms_'s `ordered` for the pair as knn_pair(feat, sq, x4, k, xt=ft) describes it.  It answers for the launch FORM
+    (fused, 16-query waves, xt).  That the kernels then take the ordered branch also needs complete order inputs (knn.hip's
+    knn_ordered()): knn_order() without guard= returns all of them, 16-byte aligned, and no ord_ok -- a change to that wrapper
+    must keep it so, or these cases would run as plain searches."""
+    import ctypes as C
+    B, N, _ = feat.shape
+    idx = torch.empty(2, B, N, k, dtype=torch.int32, device=feat.device)
+    ties = torch.empty(2, 1 + B * N, dtype=torch.int32, device=feat.device)
+    a64 = nat.KnnArgs(nat.ptr(feat), feat.stride(1), nat.ptr(sq), B, N, 64, k, nat.ptr(idx[0]), nat.ptr(ties[0]), B * N, 0)
+    a64.xt = nat.ptr(ft)
+    a3 = nat.KnnArgs(nat.ptr(x4), x4.stride(1), None, B, N, 4, k, nat.ptr(idx[1]), nat.ptr(ties[1]), B * N, 0)
+    ordered = C.c_int(-1)
+    nat.check(nat.lib().vcr_knn_forms_(C.byref(a64), C.byref(a3), C.byref(ordered), None, None), "vcr_knn_forms_")
+    return ordered.value
+
+
+def _ordered_search_keeps_the_sets(nat, B, N, k, kind, must_be_ordered=False):
     rs = np.random.RandomState(B * N + k)
     if kind == "lattice":
         xyz = rs.randint(0, 9, (B, N, 3)).astype(np.float32) / 8
@@ -932,6 +987,8 @@ def test_knn_ordered_search_keeps_the_sets(nat, B, N, k, kind):
             code |= ((qd[..., d] >> bit) & 1) << (3 * bit + d)
     key = (code << 32) | np.arange(N)[None]
     assert np.array_equal(perm.numpy(), np.argsort(key, 1, kind="stable"))
+    if must_be_ordered:
+        assert _pair_takes_the_ordered_form(nat, feat, sq, x4, ft, k) == 1, "the pair would run as a plain search"
     a0, b0 = nat.knn_pair(feat, sq, x4, k, xt=ft)
     a1, b1 = nat.knn_pair(feat, sq, x4, k, xt=ft, order=order)
     for plain, ordered in ((a0, a1), (b0, b1)):

@@ -1,459 +1,30 @@
-// Kernel 1: fused pairwise-distance + top-k (util/util.py:143-160).  The N x N distance matrix is
-// never written: distances are produced tile by tile in registers and filtered against each
-// query's current (k+2)-th best value; survivors are logged per query in LDS.
-//
-//   D_ij = (-sq_j + 2 x_i.x_j) - sq_i      (same association as util.py:157-158)
-//   idx  = top-(k+1) of D_i. by value, rank 0 dropped (util.py:159); the k kept indices are written as a SET
-//          (unordered) -- every consumer is a max over neighbours.
-//          Exact ties at the (k+1)-th value: Tensor.topk on the CPU is libstdc++'s std::nth_element (or
-//          std::partial_sort when (k+1)*64 <= N) with a value-only comparator, so WHICH of the tied candidates it
-//          keeps is an artefact of introselect's pivoting / the heap's shape.  The value lists here carry one entry
-//          more than needed, which makes such a tie visible (about 1 row in 10^4 in fp32); those rows are re-done by
-//          knn_tiebreak_kernel, a replica of the libstdc++ algorithms, so that the neighbour SETS equal the
-//          reference's on every row (validated against torch.topk on tie-heavy inputs).  A row WITHOUT a boundary tie
-//          has a set that depends on the values only; without tie_scratch a boundary tie keeps the tied candidates
-//          that were scanned first.
-//          A shared BEST value (copies of a point, or a neighbour so close that its distance rounds to the point's own --
-//          fp32 self-distances are not exactly 0) is the other tie that matters: util.py:159 drops whichever entry topk
-//          returns first, and that is position 0 after ATen's sort of the selected entries (std::sort of the first k after
-//          nth_element, or partial_sort's heap sort), not the lowest index.  Such rows are listed and replayed as well; the
-//          replay ends with a port of that sort.  (Found in round 6 by the vcrnetIter reuse soak: two launch forms of the
-//          Cartesian search logged such a pair in different orders and kept different copies.)
-//
-// Selection, round 2 (measured on the round-1 kernels: 40 % of their time went into the sorted-insert network that
-// moved (value, index) pairs through 22-42 register slots, ~100 issue slots per insertion):
-//   * registers hold the sorted top-KS VALUES only: an insertion is one v_med3_f32 per slot, no compares, no index
-//     traffic.  The list of a query is spread over the lanes that share the query (2 for the MFMA layout, 4 in the
-//     Cartesian kernel); lane segment s takes min(d, last value of segment s-1) -- what falls off the segment above,
-//     known before the insertion -- so the segments need one cross-lane move per insertion and no chain;
-//   * every candidate that passed the filter stays in the query's LDS log as (value, index).  The log is compacted
-//     in place against the current KS-th best value whenever it runs out of room (entries strictly above it, at most
-//     KS-1, plus as many equal ones as the list itself holds), and once more at the end against the (k+2)-th best
-//     value: what is left ARE the k+1 neighbours.
-//
-// C == 64: v_mfma_f32_32x32x2_f32 with candidates as MFMA rows and queries as MFMA columns: lanes l and l+32 own one
-//          query column and 16 candidate rows each (cross-lane: v_permlane32_swap).  The k order of the MFMA chain is
-//          the natural one (step s multiplies k = 2s, 2s+1) and -sq_j/2 rides along as a 33rd k-step: together with
-//          the pointwise kernel's reference-ordered features and norms the distance matrix is BIT-IDENTICAL to the
-//          reference's (CPU sgemm = k-ascending fma chain; verified), so the feature-space neighbour sets never flip.
-//          S waves of a workgroup may share a query tile and split the candidate tiles (k <= 20; S = 2 puts two waves
-//          on every SIMD at BASELINE configs[1]); their value lists and logs are folded at the end.
-// C == 4 : Cartesian xyz4 rows on the VALU: four lanes (one DPP quad) per query, 16 queries per wave, each lane
-//          scanning every fourth candidate (cross-lane: DPP quad_perm).
+// Kernel 1: fused pairwise-distance + top-k (util/util.py:143-160).  The N x N distance matrix is never written: distances are produced
+// tile by tile in registers and filtered against each query's current (k+2)-th best value; survivors are logged per query in LDS
+// (knn_select.h).  D_ij = (-sq_j + 2 x_i.x_j) - sq_i (the association of util.py:157-158); idx = top-(k+1) of D_i. by value, rank 0
+// dropped (util.py:159), written as a SET; rows with an exact tie at the boundary or at the best value are replayed (knn_tiebreak.h).
+// Bit-exactness: every body forms the dot product as a k-ASCENDING fma chain, then -sq_j/2 as one more k-step, then 2 acc - sq_i
+// (doubling is exact): with the pointwise kernel's reference-ordered features and norms the distance matrix is BIT-IDENTICAL to the
+// reference's (CPU sgemm = k-ascending fma chain; verified), so every body and launch form gives the same sets.
+// Three bodies; knn_plan() decides which one a search runs, pair_form() whether the two searches of a pass share a launch:
+//   knn64c_body  16-query waves on v_mfma_f32_16x16x4_f32, four unsplit waves: feature rows (C == 64) from 1024 groups of 16 queries
+//                up, every unsplit Cartesian search (C == 4: ONE MFMA per tile), the fused knn_pair_kernel, the ordered search.
+//   knn64_body   32-query waves on v_mfma_f32_32x32x2_f32 (C == 64), S = 1 / 2 / 4 waves splitting a query group's candidates: small grids.
+//   knn3_body    Cartesian rows on the VALU, one DPP quad per query, S = 2 / 4: the small Cartesian grids.
 #include "common.h"
 #include "vcr_internal.h"
+#include "knn_tiebreak.h"
+#include "knn_select.h"
 
 namespace {
 
-constexpr int TILE = 32;            // candidates per MFMA tile
-// log entries per query: room for the KS-1 entries a compaction can leave, the <= 16 a step adds, and slack so that
-// compactions stay rare
-// Log capacity per query.  Measured for the MFMA kernel at k = 20 (MI355X, 32 clouds): 96 / 128 entries make the kernel
-// alone 7 % faster at N = 1024 (fewer compactions) but cost the second workgroup per CU at N = 2048 (+20 %) and the
-// co-residency of the one-launch kNN pair (+20 %): 64 stays.
+constexpr int TILE = 32;            // candidates per MFMA tile of the 32-query body
 constexpr int KNN_MAX_N = 131072;                       // points per cloud the kNN entry points accept: the largest size that is validated
                                                          // (sampled rows at N = 70 001 and 131 072, tests/test_hip_kernels.py; beyond: VCR_EUNSUPPORTED
                                                          // rather than an unvalidated result).  The whole forward keeps its own, lower limit: forward.hip
 static bool knn_rows_overflow(const vcr_knn_args* a) { return (long long)a->B * a->N >= (1ll << 31); }   // row = b * N + q is an int
-constexpr int KNN_PEND_MFMA = 64;
-struct GeomMfma;
-struct GeomCol16;
-// 16-query kernels (k <= 20): 72 -- the most that keeps four workgroups per CU (4 x (76 rows x 16 queries x 8 B x 4 waves
-// + the tie list) = 157 KB of the 160): a compaction then frees 35 slots instead of 27.  Measured against 64: the pair
-// launch 151.4 -> 147.7 us at BASELINE configs[1], 147.5 -> 136.7 at N = 768 (configs[2]), 439 -> 432 at N = 2048.
 constexpr int KNN_ORD_NEAR = 4;                          // tiles on either side of the own one scanned first
 constexpr int KNN_ORD_MAX_TILES = 512;                   // the ordered search's wave-uniform tile mask: clouds of up to 8192 points
-constexpr int KNN_PEND_K40 = 96;                         // k = 21 .. 40 (lists of 42)
-constexpr int KNN_PEND_COL16 = 72;                       // (the sweeps: profiles/experiments/probe_build.py --set NAME=VALUE)
-template <class G, int KS> constexpr int pend_of() {
-  return KS > 22 ? KNN_PEND_K40 : std::is_same<G, GeomMfma>::value ? KNN_PEND_MFMA : std::is_same<G, GeomCol16>::value ? KNN_PEND_COL16 : 64;
-}
-
 // "//@probe ..." lines: inert here, uncommented by profiles/experiments/probe_build.py (phase clocks of wave 0).
-
-// In-kernel tie replay (vcr_knn_args.tie_inline, set by the host when a row's replay image fits the workgroup's LDS): the
-// rows of a workgroup whose (k+1)-th and (k+2)-th values tie are listed in LDS and replayed by that workgroup itself
-// once its four waves have written their results -- the separate, latency-bound replay launch (36 us at BASELINE
-// configs[1] for a handful of rows) disappears; only the few workgroups that own a tied row run ~20 us longer.
-constexpr int BLK_TIES = 64;                             // a 64-query workgroup cannot list more
-constexpr int TB_LDS_PAD = 8;                            // see tiebreak_row (8: N = 10 091 still fits 160 KB)
-__host__ __device__ constexpr size_t tiebreak_lds(int N) { return TB_LDS_PAD + (size_t)N * 16 + 256 + (16 + 2 * 256 + 2) * 4; }
-// the list sits behind whichever is larger, the waves' logs or the replay's LDS image of a row
-__host__ __device__ constexpr size_t inline_tie_offset(size_t log_bytes, int N) {
-  return ((log_bytes > tiebreak_lds(N) ? log_bytes : tiebreak_lds(N)) + 15) & ~(size_t)15;
-}
-constexpr size_t INLINE_TIE_MAX_LDS = 40 * 1024;         // four workgroups per CU must still fit
-__device__ void tiebreak_row(const vcr_knn_args& a, int row, unsigned char* smem, unsigned char* gwork);
-// gwork (tie_inline == 2): the row image lives in THIS workgroup's 16 N-byte slot of vcr_knn_args.tie_work instead of LDS --
-// rows too long for an LDS image beside three or four resident workgroups (N > ~2400) are then replayed by the workgroup
-// that found them too, under the other workgroups' scans, instead of by a separate launch (0.16 ms at 64 x 4096, k = 40).
-__device__ __forceinline__ void replay_block_ties(const vcr_knn_args& a, int* blk_ties, unsigned char* smem, unsigned char* gwork = nullptr) {
-  __syncthreads();                                       // every wave is done with its log: the LDS is free
-  const int n = min(blk_ties[0], BLK_TIES);
-  int rows[4];                                           // (the list itself lies behind the replay's LDS image)
-  for (int t0 = 0; t0 < n; t0 += 4) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) rows[u] = t0 + u < n ? blk_ties[1 + t0 + u] : -1;
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (rows[u] >= 0) tiebreak_row(a, rows[u], smem, gwork);
-  }
-}
-
-// Row whose (k+1)-th and (k+2)-th best values are equal: hand it to knn_tiebreak_kernel (ties[0] = count).
-__device__ __forceinline__ void report_tie(int32_t* ties, int cap, int row) {
-  if (!ties) return;
-  const int pos = atomicAdd(&ties[0], 1);
-  if (pos < cap) ties[1 + pos] = row;
-}
-
-// ---- lane geometry of a query's lanes.  Every cross-lane move is issued with all lanes active and only its RESULT
-// is selected per lane (DPP / permlane reads of switched-off lanes return 0).
-struct GeomMfma {                    // 32 query columns, lanes l and l+32 share one: segment = lane >> 5
-  static constexpr int COLS = 32, LPQ = 2;
-  static constexpr bool SPLIT_COMPACT = false;
-  __device__ static __forceinline__ int ord(int) { return 0; }
-  __device__ static __forceinline__ int prefix(int x, int, int& total) { total = x; return 0; }
-  __device__ static __forceinline__ int col(int lane) { return lane & 31; }
-  __device__ static __forceinline__ int seg(int lane) { return lane >> 5; }
-  // x of segment `which` (0 / 1), in every lane of the column (v_permlane32_swap: result 0 = the lower half's values
-  // in both halves, result 1 = the upper half's)
-  __device__ static __forceinline__ int from_seg(int x, int which) {
-    const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-    return which ? r[1] : r[0];
-  }
-  __device__ static __forceinline__ int from_prev(int x, int, int) { return from_seg(x, 0); }   // only segment 1 has a predecessor
-  __device__ static __forceinline__ int prev_addr(int) { return 0; }
-  __device__ static __forceinline__ int col_sum(int x, int sg) { return x + from_seg(x, sg ^ 1); }
-};
-struct GeomCol16 {                   // v_mfma_f32_16x16x4_f32 layout: 16 query columns, lanes c, c+16, c+32, c+48 share one.
-  // The value list of a query runs through its four lanes in the row order 0 -> 1 -> 3 -> 2 (seg 0..3), chosen so that
-  // every segment's predecessor is ONE row swap away: v_permlane16_swap exchanges rows (0,1) and (2,3),
-  // v_permlane32_swap rows (0,2) and (1,3).  With both operands = x, swap16 returns {even row of the pair, odd row of
-  // the pair} in every lane of the pair, swap32 {row of the lower half, row of the upper half} in both halves.
-  static constexpr int COLS = 16, LPQ = 4;
-  __device__ static __forceinline__ int col(int lane) { return lane & 15; }
-  __device__ static __forceinline__ int seg(int lane) { const int q = lane >> 4; return q ^ (q >> 1); }   // 0,1,3,2
-  __device__ static __forceinline__ int from_seg(int x, int which) {      // `which` is wave-uniform
-    const int q = which ^ (which >> 1);                                   // the row that holds segment `which`
-    const auto a = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-    const int v = (q & 1) ? a[1] : a[0];
-    const auto b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    return (q >> 1) ? b[1] : b[0];
-  }
-  // segment sg - 1's value (sg == 0: unused): row 1 <- row 0; row 3 <- row 1; row 2 <- row 3.  ONE ds_bpermute_b32 on the
-  // otherwise idle LDS crossbar instead of both row swaps, their operand copies and the selects (9 VALU instructions of
-  // the 17 an insertion cost -- the drains are bound by VALU issue, four waves per SIMD cover the longer latency).
-  // (The same exchange for the per-tile / per-compaction-round prefixes was measured and is slower: those chains are
-  // short and wait for the crossbar.)
-  __device__ static __forceinline__ int prev_addr(int lane) {
-    const int q = lane >> 4, pq = q == 1 ? 0 : q == 3 ? 1 : q == 2 ? 3 : 0;
-    return 4 * (16 * pq + (lane & 15));
-  }
-  __device__ static __forceinline__ int from_prev(int x, int, int pa) { return __builtin_amdgcn_ds_bpermute(pa, x); }
-  __device__ static __forceinline__ int col_sum(int x, int sg) {
-    const int q = sg ^ (sg >> 1);
-    const auto a = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-    x += (q & 1) ? a[0] : a[1];
-    const auto b = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-    return x + ((q >> 1) ? b[0] : b[1]);
-  }
-  // exclusive prefix of x over the four lanes of a column in ROW order (row = lane >> 4), and the total
-  static constexpr bool SPLIT_COMPACT = true;            // log rows PEND .. PEND + 3 exist (one trash row per lane row)
-  __device__ static __forceinline__ int ord(int lane) { return lane >> 4; }
-  __device__ static __forceinline__ int prefix(int x, int row, int& total) {
-    const auto a = __builtin_amdgcn_permlane16_swap(x, x, false, false);      // {even row, odd row} of the pair
-    const int pair_total = a[0] + a[1];
-    const auto b = __builtin_amdgcn_permlane32_swap(pair_total, pair_total, false, false);   // {rows 0+1, rows 2+3}
-    total = b[0] + b[1];
-    return ((row & 1) ? a[0] : 0) + ((row >> 1) ? b[0] : 0);
-  }
-};
-struct GeomQuad {                    // 16 queries, one DPP quad each: segment = lane & 3
-  static constexpr int COLS = 16, LPQ = 4;
-  static constexpr bool SPLIT_COMPACT = false;
-  __device__ static __forceinline__ int ord(int) { return 0; }
-  __device__ static __forceinline__ int prefix(int x, int, int& total) { total = x; return 0; }
-  __device__ static __forceinline__ int col(int lane) { return lane >> 2; }
-  __device__ static __forceinline__ int seg(int lane) { return lane & 3; }
-  __device__ static __forceinline__ int from_seg(int x, int which) {
-    const int a = __builtin_amdgcn_mov_dpp(x, 0x00, 0xF, 0xF, true), b = __builtin_amdgcn_mov_dpp(x, 0x55, 0xF, 0xF, true);
-    const int c = __builtin_amdgcn_mov_dpp(x, 0xAA, 0xF, 0xF, true), d = __builtin_amdgcn_mov_dpp(x, 0xFF, 0xF, 0xF, true);
-    return which == 0 ? a : which == 1 ? b : which == 2 ? c : d;
-  }
-  __device__ static __forceinline__ int from_prev(int x, int, int) { return __builtin_amdgcn_mov_dpp(x, 0x90, 0xF, 0xF, true); }
-  __device__ static __forceinline__ int prev_addr(int) { return 0; }
-  __device__ static __forceinline__ int col_sum(int x, int) {
-    x += __builtin_amdgcn_mov_dpp(x, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-    x += __builtin_amdgcn_mov_dpp(x, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-    return x;
-  }
-};
-template <class G> __device__ __forceinline__ float gf_from_seg(float x, int which) {
-  return __int_as_float(G::from_seg(__float_as_int(x), which));
-}
-
-// ---- per-query selection state of one wave: sorted top-KS values in registers (T per lane), (value, index) log in LDS
-// v_med3_f32 a, b, (+-inf in an SGPR): see Selector::insert
-__device__ __forceinline__ float med3_inf(float a, float b, float inf) {
-  float r;
-  asm("v_med3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(inf));
-  return r;
-}
-template <class G, int KS>
-struct Selector {
-  static constexpr int PEND = pend_of<G, KS>();
-  static constexpr int T = (KS + G::LPQ - 1) / G::LPQ;   // values per lane; the list holds LPQ*T >= KS values
-  static constexpr int TL = (KS - 1) / T, TS = (KS - 1) % T;   // segment / slot of rank KS-1: the filter threshold
-  float v[T];
-  float* lv; int* li;                                    // log [PEND + 1][COLS]; row PEND swallows the writes of lanes
-                                                         // that have nothing to log (branch-free appends)
-  int cnt, done;                                         // entries logged / already inserted (same in a query's lanes)
-  float thr;                                             // max(thr0, rank KS-1 value): nothing <= thr can be a neighbour
-  float thr0;                                            // filter floor taken from a sample of the candidates (see sample_floor)
-  int col, sg, pa;
-
-  __device__ __forceinline__ void init(float* lv_, int* li_, int lane, float floor0 = VCR_NEG_INF) {
-    lv = lv_; li = li_; cnt = 0; done = 0; thr = thr0 = floor0; col = G::col(lane); sg = G::seg(lane); pa = G::prev_addr(lane);
-#pragma unroll
-    for (int t = 0; t < T; ++t) v[t] = VCR_NEG_INF;
-  }
-  // one value into the query's list, all segments at once (inserting -inf or anything <= the last value is a no-op)
-  __device__ __forceinline__ void insert(float d) {
-    const float pb = __int_as_float(G::from_prev(__float_as_int(v[T - 1]), sg, pa));
-    // (v_med3_f32 with an infinite third operand: min / max in ONE instruction.  Spelled as inline assembly: hipcc folds
-    // the builtin with an infinite constant back into v_min / v_max plus a NaN-quieting v_max x, x per operand -- four
-    // instructions for the clamp, three for the head of the list)
-    d = med3_inf(d, sg ? pb : __builtin_huge_valf(), VCR_NEG_INF);       // min(d, predecessor's last); segment 0 has none
-#pragma unroll
-    for (int t = T - 1; t >= 1; --t) v[t] = __builtin_amdgcn_fmed3f(v[t - 1], d, v[t]);
-    v[0] = med3_inf(v[0], d, __builtin_huge_valf());
-  }
-  __device__ __forceinline__ void refresh_thr() {
-    const float mine = v[TS];
-    thr = fmaxf(thr0, gf_from_seg<G>(mine, TL));
-  }
-  // The floor came from a sample: it is only valid if at least KS candidates lie above it.  False -> the list is not
-  // full although a floor was used: the caller scans again without one.
-  __device__ __forceinline__ bool floor_held() const {
-    const float last = gf_from_seg<G>(v[TS], TL);
-    return !(thr0 > VCR_NEG_INF) || last > VCR_NEG_INF;
-  }
-  // value at global rank r (wave-uniform r) in every lane of the column
-  __device__ __forceinline__ float rank_value(int r) const {
-    const int rs = r / T, rt = r % T;
-    int bits = 0;                                        // (an OR of masked words: a select chain over v[] would be
-#pragma unroll                                           // turned into a dynamically indexed scratch array)
-    for (int t = 0; t < T; ++t) bits |= (rt == t ? -1 : 0) & __float_as_int(v[t]);
-    return gf_from_seg<G>(__int_as_float(bits), rs);
-  }
-  // insert the values logged since the last drain.  Four log reads are in flight per round trip: the loop is bound by
-  // LDS latency, not by the 1-med3-per-slot network.
-  __device__ __forceinline__ void drain() {
-    int i = done;
-    while (__any(i < cnt)) {
-      float d[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) d[u] = lv[min(i + u, PEND - 1) * G::COLS + col];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) insert(i + u < cnt ? d[u] : VCR_NEG_INF);      // idle lanes insert -inf: a no-op
-      i += 4;
-    }
-    done = cnt;
-    refresh_thr();
-  }
-  // keep the log entries above x, plus at most `emax` equal to x (the earliest logged); cnt = done = kept
-  __device__ __forceinline__ void compact(float x, int emax) {
-    if constexpr (G::SPLIT_COMPACT) {
-      // the four lanes of a column take one entry each per round (the loop below has every lane walk all four: four
-      // times the LDS instructions): keep flags and write positions come from prefixes over the lanes in row order, so
-      // the kept entries stay in logging order and the "at most emax equal to x, the earliest" rule is unchanged
-      int w = 0, ne = 0;
-      const int od = G::ord((int)__lane_id());            // (recomputed here: a register less across the scan)
-      for (int i = 0; __any(i < cnt); i += 4) {
-        const int ii = i + od;
-        const bool valid = ii < cnt;
-        const int ic = min(ii, PEND - 1);
-        const float d = lv[ic * G::COLS + col];
-        const int j = li[ic * G::COLS + col];
-        const bool gt = valid && d > x, eq = valid && d == x;
-        // ONE prefix for both counts (packed: entries above x in the low half, entries equal to x in the high half); of
-        // the equal ones the first `cap` still wanted are kept, so their kept-prefix is min(prefix, cap)
-        int tot;
-        const int pre = G::prefix((gt ? 1 : 0) | (eq ? 0x10000 : 0), od, tot);
-        const int cap = max(emax - ne, 0), epre = pre >> 16, etot = tot >> 16;
-        const bool keep = gt || (eq && epre < cap);
-        const int kpre = (pre & 0xffff) + min(epre, cap);
-        const int wr = keep ? w + kpre : PEND + od;      // w + kpre <= i + od: in place; reads of the round precede its writes
-        lv[wr * G::COLS + col] = d;
-        li[wr * G::COLS + col] = j;
-        w += (tot & 0xffff) + min(etot, cap);
-        ne += min(etot, cap);
-      }
-      cnt = done = w;
-      return;
-    }
-    int w = 0, ne = 0;
-    for (int i = 0; __any(i < cnt); i += 4) {
-      float d[4];
-      int j[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {                      // all four entries are in registers before any is rewritten
-        const int ii = min(i + u, PEND - 1);
-        d[u] = lv[ii * G::COLS + col];
-        j[u] = li[ii * G::COLS + col];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const bool eq = d[u] == x && ne < emax;
-        const bool keep = i + u < cnt && (d[u] > x || eq);
-        const int wr = keep ? w : PEND;                  // w <= i + u: in place (the lanes of a column write the same words)
-        lv[wr * G::COLS + col] = d[u];
-        li[wr * G::COLS + col] = j[u];
-        w += keep ? 1 : 0;
-        ne += (keep && eq) ? 1 : 0;
-      }
-    }
-    cnt = done = w;
-  }
-  __device__ __forceinline__ int count_above(float x) const {
-    int c = 0;
-#pragma unroll
-    for (int t = 0; t < T; ++t) c += v[t] > x ? 1 : 0;
-    return G::col_sum(c, sg);
-  }
-  // make room for the next step (<= 16 new entries per query)
-  __device__ __forceinline__ void make_room() {
-    if (__any(cnt > PEND - 16)) {
-      drain();
-      compact(thr, KS - count_above(thr));
-    }
-  }
-};
-
-// Filter floor from a SAMPLE of the candidates.  A streaming top-k logs k (1 + ln(n / k)) candidates per query because
-// its threshold starts at -inf; most of those are entries the first few hundred candidates push through a list that
-// later ones empty again.  A values-only pre-pass (R v_med3 per candidate) over a lane's share of the first 256
-// candidates keeps its R best; the smallest of the lanes' R-th values is a floor with at least LPQ * R - 1 sample
-// values strictly above it, and R is chosen so that this is >= KS: the floor is below the final KS-th best value by
-// construction, for ANY ordering of the cloud.  The scan proper then starts with a useful threshold: at N = 1024,
-// k = 20 it logs ~55 candidates per query instead of ~125, and the log rarely needs compacting.  (Exact ties AT the
-// floor value could still leave fewer than KS values strictly above it; that is checked at the end -- floor_held() --
-// and such a wave scans again without a floor.)
-constexpr int SAMPLE = 256;
-template <int R>
-struct SampleNet {
-  float s[R];
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int t = 0; t < R; ++t) s[t] = VCR_NEG_INF;
-  }
-  __device__ __forceinline__ void insert(float d) {
-#pragma unroll
-    for (int t = R - 1; t >= 1; --t) s[t] = __builtin_amdgcn_fmed3f(s[t - 1], d, s[t]);
-    s[0] = med3_inf(s[0], d, __builtin_huge_valf());
-  }
-};
-template <class G> __device__ __forceinline__ float col_min(float x, int sg) {   // min over the lanes of a query
-  float m = x;
-#pragma unroll
-  for (int w = 0; w < G::LPQ; ++w) m = fminf(m, gf_from_seg<G>(x, w));
-  (void)sg;
-  return m;
-}
-
-// Final stage shared by both kernels: the log holds every candidate above the (k+2)-th best value; fold the lists /
-// logs of the S waves of a query group into wave part 0, reduce the log to the k+1 best, drop rank 0, write the set.
-// perm (ordered search): q and the logged indices are RANKS of the cloud's Morton order; the kept entries are translated to
-// point indices before the rank-0 rule and the output, which goes to the row of the point at rank q
-template <class G, int KS, int S>
-__device__ __forceinline__ void finish(Selector<G, KS>& sel, const vcr_knn_args& a, int b, int q, int wave, int part,
-                                       unsigned char* smem, int* blk_ties = nullptr, const int32_t* perm = nullptr) {
-  constexpr int T = Selector<G, KS>::T;
-  constexpr int PEND = Selector<G, KS>::PEND;
-  constexpr int AREA = 2 * (PEND + 1) * G::COLS;         // floats per wave
-  sel.drain();
-  if (S > 1) {
-    // every wave first shrinks its log to its own top-KS and parks its sorted values behind it (KS <= 22: 22 + 24 <= 64)
-    sel.compact(sel.thr, KS - sel.count_above(sel.thr));
-#pragma unroll
-    for (int t = 0; t < T; ++t) sel.lv[(PEND - G::LPQ * T + sel.sg * T + t) * G::COLS + sel.col] = sel.v[t];
-    if (sel.sg == 0) sel.li[(PEND - 1) * G::COLS + sel.col] = sel.cnt;
-    __syncthreads();
-    if (part == 0) {
-      for (int p = 1; p < S; ++p) {
-        const float* ov = reinterpret_cast<const float*>(smem) + (size_t)(wave + p) * AREA;
-        for (int t = 0; t < KS; ++t) sel.insert(ov[(PEND - G::LPQ * T + t) * G::COLS + sel.col]);
-      }
-      sel.refresh_thr();
-    }
-  }
-  if (part != 0) return;
-  const float vk = sel.rank_value(a.k), vk1 = sel.rank_value(a.k + 1);       // ranks k+1 and k+2 (KS >= k+2)
-  const int need = a.k + 1 - sel.count_above(vk1);      // neighbours that EQUAL the (k+2)-th value: 0 unless tied
-  sel.compact(vk1, need);
-  if (S > 1) {                                           // append the other waves' qualifying entries
-    int ne = 0;
-    for (int i = 0; i < sel.cnt; ++i) ne += sel.lv[i * G::COLS + sel.col] == vk1 ? 1 : 0;
-    for (int p = 1; p < S; ++p) {
-      const float* ov = reinterpret_cast<const float*>(smem) + (size_t)(wave + p) * AREA;
-      const int* oi = reinterpret_cast<const int*>(ov + (PEND + 1) * G::COLS);
-      const int oc = oi[(PEND - 1) * G::COLS + sel.col];
-      for (int i = 0; __any(i < oc); ++i) {
-        const int ii = min(i, PEND - 1);
-        const float d = ov[ii * G::COLS + sel.col];
-        const int j = oi[ii * G::COLS + sel.col];
-        const bool eq = d == vk1 && ne < need;
-        const bool keep = i < oc && (d > vk1 || eq) && sel.cnt < PEND;
-        if (keep) { sel.lv[sel.cnt * G::COLS + sel.col] = d; sel.li[sel.cnt * G::COLS + sel.col] = j; }
-        sel.cnt += keep ? 1 : 0;
-        ne += (keep && eq) ? 1 : 0;
-      }
-    }
-  }
-  // rank 0 = the largest value (the point itself): dropped.  When that value is SHARED (duplicate points, or a neighbour so
-  // close that its distance rounds to the point's own), WHICH of the tied entries Tensor.topk returns first is an outcome of
-  // its sort (util.py:159 then drops that one and keeps the others): such a row is replayed like a boundary tie (best_shared
-  // below; tiebreak_row sorts the kept entries the way ATen does).  Without tie_scratch: the first logged is dropped.
-  // (Whether it is shared is read off the sorted value list: its two best entries are equal.)
-  // (-inf == -inf is no tie: a query with fewer than two finite scores -- its own coordinate non-finite -- has nothing to replay)
-  const bool best_shared = sel.rank_value(0) == sel.rank_value(1) && sel.rank_value(1) > VCR_NEG_INF;
-  int imax = 0;
-  float vmax = VCR_NEG_INF;
-  if (perm) {
-    // (the plain scan logs in index order, so "the first logged" is the LOWEST point index among the largest values)
-    for (int i = sel.sg; i < sel.cnt; i += G::LPQ) sel.li[i * G::COLS + sel.col] = perm[sel.li[i * G::COLS + sel.col]];
-    int jmax = 0x7fffffff;
-    for (int i = 0; __any(i < sel.cnt); ++i) {
-      const int ic = min(i, PEND - 1);
-      const float d = i < sel.cnt ? sel.lv[ic * G::COLS + sel.col] : VCR_NEG_INF;
-      const int j = sel.li[ic * G::COLS + sel.col];
-      if (d > vmax || (d == vmax && i < sel.cnt && j < jmax)) { vmax = d; imax = i; jmax = j; }
-    }
-  } else {
-  for (int i = 0; __any(i < sel.cnt); ++i) {
-    const float d = i < sel.cnt ? sel.lv[min(i, PEND - 1) * G::COLS + sel.col] : VCR_NEG_INF;
-    if (d > vmax) { vmax = d; imax = i; }
-  }
-  }
-  if (q < a.N) {
-    if (perm) q = perm[q];
-    int32_t* o = a.idx + ((size_t)b * a.N + q) * a.k;
-    for (int i = sel.sg; i < sel.cnt && i <= a.k; i += G::LPQ)
-      if (i != imax) o[i - (i > imax ? 1 : 0)] = sel.li[i * G::COLS + sel.col];
-    // A short list -- NaN scores never pass the filter: the query's own coordinate is non-finite, or its cloud has fewer than
-    // k + 1 finite points -- leaves slots unwritten: they take the query's own index, so that every slot is a row of its cloud.
-    for (int i = min(sel.cnt, a.k + 1) - (sel.cnt > 0 ? 1 : 0) + sel.sg; i < a.k; i += G::LPQ) o[i] = q;
-    if (sel.sg == 0 && ((vk1 == vk && vk1 > VCR_NEG_INF) || best_shared)) {
-      if (blk_ties) {                                    // replayed by this very workgroup (replay_block_ties)
-        const int pos = atomicAdd(&blk_ties[0], 1);
-        if (pos < BLK_TIES) blk_ties[1 + pos] = b * a.N + q;
-      } else {
-        report_tie(a.tie_scratch, a.tie_cap, b * a.N + q);
-      }
-    }
-  }
-}
 
 // ---------------------------------------------------------------- C == 64 (MFMA)
 // Workgroup = W waves = W/S query tiles of 32 queries; wave (qt, part) scans candidate tiles part, part+S, ...
@@ -570,28 +141,13 @@ __device__ __forceinline__ void knn64_body(const vcr_knn_args& a, int bx, int b)
       //@probe VCR_PROBE_ACC(5);
     }
   };
-  // sample pre-pass over this wave's first SAMPLE candidates (full tiles only), when it has at least twice as many
-  constexpr int T0 = SAMPLE / TILE, R0 = (KS + 1 + G::LPQ - 1) / G::LPQ;   // LPQ * R0 - 1 >= KS
-  const int my_tiles = part < ntiles ? (ntiles - part + S - 1) / S : 0;
-  float floor0 = VCR_NEG_INF;
-  // Measured (profiles/timeline_knn.py, N = 1024, k = 20): the floor cuts make_room 28 -> 13 us and the drains
-  // 12.5 -> 8 us per wave, and the pre-pass -- eight more tiles of loads + 33 MFMAs + pick -- costs the same 17 us back;
-  // at N = 2048 it loses 5 %.  Distances are too expensive here to compute a quarter of them twice: off in this kernel
-  // (the Cartesian kernel, whose distances are three FMAs, keeps it: 75 -> 65 us).
-  constexpr bool SAMPLE_FLOOR = false;
-  if (SAMPLE_FLOOR && my_tiles >= 2 * T0 + 1) {          // (+1: the last, possibly ragged, tile is never sampled)
-    SampleNet<R0> net;
-    net.init();
-    scan_tiles(part, part + S * T0, [&](int, const f32x16& acc) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) net.insert(2.f * acc[r] - sq_q);
-    });
-    floor0 = col_min<G>(net.s[R0 - 1], half);
-  }
-  sel.init(lv, reinterpret_cast<int*>(lv + (PEND + 1) * 32), lane, floor0);
+  // (no sample floor here: a values-only pre-pass over the first candidates was measured a loss at C == 64, where a sampled tile costs
+  //  its 33 MFMAs a second time -- figures in profiles/NOTES.md, round 6, the kNN source split; the Cartesian searches keep theirs)
+  sel.init(lv, reinterpret_cast<int*>(lv + (PEND + 1) * 32), lane);
   scan_tiles(part, ntiles, select_body);
   sel.drain();
-  if (__any(!sel.floor_held())) {                        // the sample misjudged some query of this wave: scan without a floor
+  // (never taken -- no floor, the compiler drops it; without it in the source the S = 1 kernels swap two instructions, NOTES.md)
+  if (__any(!sel.floor_held())) {
     sel.init(lv, reinterpret_cast<int*>(lv + (PEND + 1) * 32), lane);
     scan_tiles(part, ntiles, select_body);
   }
@@ -806,7 +362,7 @@ __device__ __forceinline__ void knn64c_body(const vcr_knn_args& a, int bx, int b
     const int T = ntiles, g = q0 / CT;
     int lo = max(0, g - NEAR), hi = min(T, g + NEAR + 1);
     if (hi - lo < 2 * NEAR + 1) { if (lo == 0) hi = min(T, 2 * NEAR + 1); else lo = max(0, T - (2 * NEAR + 1)); }
-    // the two-tile step of scan_all over an arbitrary tile sequence (next() = the next tile, -1 at the end; wave-uniform)
+    // the two-tile step of scan_all over a tile sequence (next() = the next tile, -1 at the end; wave-uniform); see under ordered_scan
     auto scan_seq = [&](auto&& next) {
       int tA = next(), tB = tA >= 0 ? next() : -1;
       if (tA < 0) return;
@@ -960,6 +516,10 @@ __device__ __forceinline__ void knn64c_body(const vcr_knn_args& a, int bx, int b
   };
   // (a generic lambda behind a wrapper, as the code was measured: a plain one is the same search but changes the ORD kernels' register
   // allocation)
+  // (The two-tile step stays written out in scan_prologue + scan_all, in scan_seq and, the single chain, in ceval: stated once as
+  // fetch2 / take2 / chains it changed the code of the six knn64c_kernel, the four 16-query and the two ordered knn_pair_kernel
+  // instantiations (equal resources; s_nop / s_waitcnt moved, the ordered ones -8 / -6 s_waitcnt and a branch less), and their timing
+  // against the parent was not measured.  A fix to the prefetch or the norm step goes into all three places.  NOTES.md, round 6.)
   [[maybe_unused]] auto ordered_scan = [&]() { ordered_scan_impl(std::false_type{}); };
   // C == 4: filter floor from a sample (see SampleNet): the first 256 candidates' values only -- 16 MFMAs -- give a
   // threshold the scan proper starts with (the VALU kernel: 75 -> 65 us; distances are one MFMA per tile here, so the
@@ -1155,449 +715,6 @@ __global__ __launch_bounds__(256, 2) void knn_pair_small_kernel(vcr_knn_args a64
     if constexpr (S3 == 1) knn64c_body<KS, 4, 4>(a3, lin % gx3, lin / gx3);   // (unsplit: the MFMA body, as vcr_knn_f32 launches it)
     else knn3_body<KS, S3>(a3, lin % gx3, lin / gx3);
   }
-}
-
-// ---------------------------------------------------------------- exact replica of Tensor.topk's tie-breaking
-// Sequential port of libstdc++'s std::nth_element (__introselect: median-of-three to first, unguarded partition,
-// depth limit 2 log2 n with __heap_select fallback, final insertion sort) and of std::partial_sort's __heap_select,
-// on (value, index) pairs ordered by VALUE ONLY, exactly as ATen's CPU topk runs them (TopKImpl: queue[j] = (x[j], j);
-// partial_sort when k*64 <= n, else nth_element(k-1) + sort of the first k-1).  Only the SET of the first K entries
-// matters here.  One thread per tied row; rows are rare.
-struct PairArr {
-  float* v; int* id;
-  __device__ __forceinline__ bool gt(int a, int b) const { return v[a] > v[b]; }
-  __device__ __forceinline__ void swap(int a, int b) {
-    const float tv = v[a]; v[a] = v[b]; v[b] = tv;
-    const int ti = id[a]; id[a] = id[b]; id[b] = ti;
-  }
-};
-
-__device__ void tb_push_heap(PairArr& q, int first, int hole, int top, float val, int vid) {
-  int parent = (hole - 1) / 2;
-  while (hole > top && q.v[first + parent] > val) {
-    q.v[first + hole] = q.v[first + parent]; q.id[first + hole] = q.id[first + parent];
-    hole = parent;
-    parent = (hole - 1) / 2;
-  }
-  q.v[first + hole] = val; q.id[first + hole] = vid;
-}
-
-__device__ void tb_adjust_heap(PairArr& q, int first, int hole, int len, float val, int vid) {
-  const int top = hole;
-  int child = hole;
-  while (child < (len - 1) / 2) {
-    child = 2 * (child + 1);
-    if (q.v[first + child] > q.v[first + child - 1]) --child;
-    q.v[first + hole] = q.v[first + child]; q.id[first + hole] = q.id[first + child];
-    hole = child;
-  }
-  if ((len & 1) == 0 && child == (len - 2) / 2) {
-    child = 2 * (child + 1);
-    q.v[first + hole] = q.v[first + child - 1]; q.id[first + hole] = q.id[first + child - 1];
-    hole = child - 1;
-  }
-  tb_push_heap(q, first, hole, top, val, vid);
-}
-
-__device__ void tb_heap_select(PairArr& q, int first, int middle, int last) {
-  const int len = middle - first;
-  if (len >= 2) {                                        // std::__make_heap
-    for (int parent = (len - 2) / 2;; --parent) {
-      tb_adjust_heap(q, first, parent, len, q.v[first + parent], q.id[first + parent]);
-      if (parent == 0) break;
-    }
-  }
-  for (int i = middle; i < last; ++i) {
-    if (q.v[i] > q.v[first]) {                           // std::__pop_heap(first, middle, i)
-      const float val = q.v[i]; const int vid = q.id[i];
-      q.v[i] = q.v[first]; q.id[i] = q.id[first];
-      tb_adjust_heap(q, first, 0, len, val, vid);
-    }
-  }
-}
-
-__device__ void tb_nth_element(PairArr& q, int first, int last, int nth, int depth) {
-  while (last - first > 3) {
-    if (depth == 0) {
-      tb_heap_select(q, first, nth + 1, last);
-      q.swap(first, nth);
-      return;
-    }
-    --depth;
-    // __unguarded_partition_pivot: median of (first+1, mid, last-1) to first, then partition [first+1, last)
-    const int mid = first + (last - first) / 2, a = first + 1, b = mid, c = last - 1;
-    if (q.gt(a, b)) {
-      if (q.gt(b, c)) q.swap(first, b);
-      else if (q.gt(a, c)) q.swap(first, c);
-      else q.swap(first, a);
-    } else if (q.gt(a, c)) q.swap(first, a);
-    else if (q.gt(b, c)) q.swap(first, c);
-    else q.swap(first, b);
-    int lo = first + 1, hi = last;
-    for (;;) {
-      while (q.gt(lo, first)) ++lo;
-      --hi;
-      while (q.gt(first, hi)) --hi;
-      if (!(lo < hi)) break;
-      q.swap(lo, hi);
-      ++lo;
-    }
-    if (lo <= nth) first = lo; else last = lo;
-  }
-  for (int i = first + 1; i < last; ++i) {               // std::__insertion_sort(first, last)
-    const float val = q.v[i]; const int vid = q.id[i];
-    if (val > q.v[first]) {
-      for (int j = i; j > first; --j) { q.v[j] = q.v[j - 1]; q.id[j] = q.id[j - 1]; }
-      q.v[first] = val; q.id[first] = vid;
-    } else {
-      int j = i;
-      while (val > q.v[j - 1]) { q.v[j] = q.v[j - 1]; q.id[j] = q.id[j - 1]; --j; }
-      q.v[j] = val; q.id[j] = vid;
-    }
-  }
-}
-
-// std::__sort_heap(first, first + len): what std::partial_sort runs on its heap, and std::sort when its depth limit runs out
-__device__ void tb_sort_heap(PairArr& q, int first, int len) {
-  while (len > 1) {
-    --len;                                               // std::__pop_heap(first, last, last)
-    const float val = q.v[first + len]; const int vid = q.id[first + len];
-    q.v[first + len] = q.v[first]; q.id[first + len] = q.id[first];
-    tb_adjust_heap(q, first, 0, len, val, vid);
-  }
-}
-
-__device__ void tb_unguarded_linear_insert(PairArr& q, int last) {
-  const float val = q.v[last]; const int vid = q.id[last];
-  int next = last - 1;
-  while (val > q.v[next]) { q.v[last] = q.v[next]; q.id[last] = q.id[next]; last = next; --next; }
-  q.v[last] = val; q.id[last] = vid;
-}
-__device__ void tb_insertion_sort(PairArr& q, int first, int last) {
-  for (int i = first + 1; i < last; ++i) {
-    if (q.v[i] > q.v[first]) {
-      const float val = q.v[i]; const int vid = q.id[i];
-      for (int j = i; j > first; --j) { q.v[j] = q.v[j - 1]; q.id[j] = q.id[j - 1]; }
-      q.v[first] = val; q.id[first] = vid;
-    } else {
-      tb_unguarded_linear_insert(q, i);
-    }
-  }
-}
-// Sequential port of libstdc++'s std::sort on [first, last) (__introsort_loop: median-of-three to first + unguarded partition
-// while a range is longer than 16, depth limit 2 log2 n with the heap sort fallback; then __final_insertion_sort) with the
-// value-only comparator: the ORDER it leaves equal values in is what decides Tensor.topk's rank 0 among tied best values.
-// Ranges here are the <= 62 kept entries of a row.  The recursion on the right-hand parts: only a part of more than 16 entries
-// has work left, the parts are disjoint (the order they are finished in does not matter) -- at most three are ever pending,
-// kept packed (first | last << 8 | depth << 16) in the caller's LDS scratch (stk[0..2]).
-__device__ void tb_sort(PairArr& q, int first, int last, int* stk) {
-  if (last - first < 2) return;
-  int depth0 = 0;
-  for (int m = last - first; m > 1; m >>= 1) ++depth0;
-  depth0 *= 2;
-  int sp = 1;
-  stk[0] = first | (last << 8) | (depth0 << 16);
-  while (sp > 0) {
-    --sp;
-    const int e = stk[sp];
-    int f = e & 255, l = (e >> 8) & 255, depth = e >> 16;
-    while (l - f > 16) {
-      if (depth == 0) {                                  // std::__partial_sort(f, l, l): heap sort of the range
-        tb_heap_select(q, f, l, l);
-        tb_sort_heap(q, f, l - f);
-        break;
-      }
-      --depth;
-      const int mid = f + (l - f) / 2, a = f + 1, b = mid, c = l - 1;
-      if (q.gt(a, b)) {
-        if (q.gt(b, c)) q.swap(f, b);
-        else if (q.gt(a, c)) q.swap(f, c);
-        else q.swap(f, a);
-      } else if (q.gt(a, c)) q.swap(f, a);
-      else if (q.gt(b, c)) q.swap(f, c);
-      else q.swap(f, b);
-      int lo = f + 1, hi = l;
-      for (;;) {
-        while (q.gt(lo, f)) ++lo;
-        --hi;
-        while (q.gt(f, hi)) --hi;
-        if (!(lo < hi)) break;
-        q.swap(lo, hi);
-        ++lo;
-      }
-      if (l - lo > 16 && sp < 3) {                       // __introsort_loop(cut, last, depth_limit): later
-        stk[sp++] = lo | (l << 8) | (depth << 16);
-      }
-      l = lo;
-    }
-  }
-  if (last - first > 16) {                               // std::__final_insertion_sort
-    tb_insertion_sort(q, first, first + 16);
-    for (int i = first + 16; i < last; ++i) tb_unguarded_linear_insert(q, i);
-  } else {
-    tb_insertion_sort(q, first, last);
-  }
-}
-
-// std::partial_sort's __heap_select(first = 0, middle = K, last = n) with the K-entry heap held ACROSS THE LANES of one
-// wave (lane j = heap[j]; K <= 64): every heap access is a v_readlane / v_writelane with a scalar index instead of a
-// dependent LDS round trip, and the scan over the n - K remaining values tests 64 of them per step.  Same compares,
-// same moves as libstdc++ (__make_heap, then __pop_heap for every v[i] > heap[0]); the values evicted to positions
-// >= K are not written back: nothing reads them again.  Returns with (hv, hid) = the kept set in lanes 0..K-1.
-struct LaneHeap {
-  float hv; int hid; int lane;
-  __device__ __forceinline__ float val(int i) const {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hv), __builtin_amdgcn_readfirstlane(i)));
-  }
-  __device__ __forceinline__ int idx(int i) const {
-    return __builtin_amdgcn_readlane(hid, __builtin_amdgcn_readfirstlane(i));
-  }
-  __device__ __forceinline__ void set(int i, float v, int id) {
-    const int si = __builtin_amdgcn_readfirstlane(i);   // (v, id) are wave-uniform: a lane-select is a writelane
-    hv = lane == si ? v : hv;
-    hid = lane == si ? id : hid;
-  }
-  __device__ void push(int hole, int top, float v, int id) {          // std::__push_heap
-    int parent = (hole - 1) / 2;
-    while (hole > top && val(parent) > v) {
-      set(hole, val(parent), idx(parent));
-      hole = parent;
-      parent = (hole - 1) / 2;
-    }
-    set(hole, v, id);
-  }
-  __device__ void adjust(int hole, int len, float v, int id) {        // std::__adjust_heap
-    const int top = hole;
-    int child = hole;
-    while (child < (len - 1) / 2) {
-      child = 2 * (child + 1);
-      if (val(child) > val(child - 1)) --child;
-      set(hole, val(child), idx(child));
-      hole = child;
-    }
-    if ((len & 1) == 0 && child == (len - 2) / 2) {
-      child = 2 * (child + 1);
-      set(hole, val(child - 1), idx(child - 1));
-      hole = child - 1;
-    }
-    push(hole, top, v, id);
-  }
-};
-
-__device__ void tb_heap_select_wave(const float* v, int n, int K, LaneHeap& h, int lane) {
-  h.hv = lane < K ? v[lane] : VCR_NEG_INF;
-  h.hid = lane;
-  h.lane = lane;
-  if (K >= 2) {
-    for (int parent = (K - 2) / 2;; --parent) {
-      h.adjust(parent, K, h.val(parent), h.idx(parent));
-      if (parent == 0) break;
-    }
-  }
-  float top = h.val(0);
-  for (int base = K; base < n; base += 64) {
-    const int x = base + lane;
-    const float c = x < n ? v[x] : VCR_NEG_INF;
-    unsigned long long mask = __builtin_amdgcn_ballot_w64(c > top);
-    while (mask) {
-      const int i = __builtin_ctzll(mask);
-      const float cv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c), __builtin_amdgcn_readfirstlane(i)));
-      h.adjust(0, K, cv, base + i);                      // __pop_heap: the candidate replaces the root
-      top = h.val(0);
-      mask = __builtin_amdgcn_ballot_w64(c > top) & ~((2ull << i) - 1ull);
-    }
-  }
-}
-
-// One __unguarded_partition_pivot pass of introselect on [first, last), run by the whole block with the SAME result
-// as the sequential loop.  With pivot p = v[first] after the median-of-three, the left scan stops at the elements
-// <= p and the right scan at the elements >= p, in order: if A lists the positions > first with v <= p (ascending)
-// and Bd the positions > first with v >= p (descending), the loop swaps A[i] <-> Bd[i] while A[i] < Bd[i] (m swaps)
-// and returns cut = min(A[m], Bd[m-1]) (A[0] when m = 0).  A / Bd are built by an ordered block compaction.
-__device__ int tb_partition_parallel(PairArr& q, int first, int last, int* A, int* Bd, int* red) {
-  const int t = threadIdx.x, nt = blockDim.x;
-  if (t == 0) {
-    const int mid = first + (last - first) / 2, a = first + 1, b = mid, c = last - 1;
-    if (q.gt(a, b)) {
-      if (q.gt(b, c)) q.swap(first, b);
-      else if (q.gt(a, c)) q.swap(first, c);
-      else q.swap(first, a);
-    } else if (q.gt(a, c)) q.swap(first, a);
-    else if (q.gt(b, c)) q.swap(first, c);
-    else q.swap(first, b);
-  }
-  __syncthreads();
-  const float pv = q.v[first];
-  const int n = last - (first + 1);
-  const int per = (n + nt - 1) / nt;
-  const int x0 = first + 1 + t * per, x1 = min(last, x0 + per);
-  int ca = 0, cb = 0;
-  for (int x = x0; x < x1; ++x) { ca += q.v[x] <= pv ? 1 : 0; cb += q.v[x] >= pv ? 1 : 0; }
-  // exclusive prefix of ca over ascending threads, exclusive SUFFIX of cb (threads to the right come first in Bd):
-  // wave-level shuffles + four wave totals through LDS
-  const int lane = t & 63, wv = t >> 6, nwv = nt >> 6;
-  int ia = ca, ib = cb;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int ua = __shfl_up(ia, o, 64), ub = __shfl_down(ib, o, 64);
-    if (lane >= o) ia += ua;
-    if (lane + o < 64) ib += ub;
-  }
-  if (lane == 63) red[wv] = ia;                          // wave totals
-  if (lane == 0) red[8 + wv] = ib;
-  __syncthreads();
-  int offa = ia - ca, offb = ib - cb, sa = 0, sb = 0;
-  for (int i = 0; i < nwv; ++i) {
-    if (i < wv) offa += red[i];
-    if (i > wv) offb += red[8 + i];
-    sa += red[i]; sb += red[8 + i];
-  }
-  __syncthreads();
-  red[16 + t] = offa; red[16 + nt + t] = offb;
-  if (t == 0) { red[2 * nt + 16] = sa; red[2 * nt + 17] = sb; }
-  __syncthreads();
-  const int na = red[2 * nt + 16], nb = red[2 * nt + 17];
-  {
-    int oa = red[16 + t];
-    for (int x = x0; x < x1; ++x) if (q.v[x] <= pv) A[oa++] = x;
-    int ob = red[16 + nt + t];                           // descending order: this chunk's elements from the right
-    for (int x = x1 - 1; x >= x0; --x) if (q.v[x] >= pv) Bd[ob++] = x;
-  }
-  __syncthreads();
-  const int lim = min(na, nb);
-  int mloc = 0;
-  for (int i = t; i < lim; i += nt) mloc += A[i] < Bd[i] ? 1 : 0;   // monotone in i: the count is the first failure
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) mloc += __shfl_xor(mloc, o, 64);
-  if (lane == 0) red[wv] = mloc;
-  __syncthreads();
-  int m = 0;
-  for (int i = 0; i < nwv; ++i) m += red[i];
-  int cut;
-  if (m == 0) cut = A[0];
-  else cut = min(m < na ? A[m] : 0x7fffffff, Bd[m - 1]);
-  __syncthreads();                                       // everyone has read A / Bd / red before the swaps reuse LDS
-  for (int i = t; i < m; i += nt) q.swap(A[i], Bd[i]);
-  __syncthreads();
-  return cut;
-}
-
-constexpr size_t TB_LDS_MAX = 160 * 1024;
-constexpr int TB_BLOCKS = 64;
-
-// One block per tied row: all threads recompute the row's N distances with the SAME arithmetic as the main kernels
-// (C == 64: the k-ascending fma chain the MFMA produces, then the -sq_j/2 step, then 2 acc - sq_i; C == 4: the VALU
-// expression of knn3_kernel), thread 0 replays the selection and rewrites the row's k indices.
-__device__ void tiebreak_row(const vcr_knn_args& a, int row, unsigned char* smem, unsigned char* gwork) {
-  float *val, *qrow;
-  int *id, *A, *Bd, *red;
-  if (!gwork) {
-    // (8 bytes of padding in front: the arrays the sequential ports walk downwards must not start at LDS offset 0.  This code
-    // reaches LDS through flat instructions wherever val / id may also be global (see below); the compiler turns the `v[j - 1]`
-    // of a descending loop into (base - 4) + an immediate offset of 4, and a flat address below the LDS aperture faults
-    // whatever the offset -- MEMORY_APERTURE_VIOLATION in the replay launch, located with rocgdb when the rank-0 sort was
-    // added.  The ports never index more than one entry below their position.)
-    val = reinterpret_cast<float*>(smem) + TB_LDS_PAD / 4;
-    id = reinterpret_cast<int*>(val + a.N);
-    qrow = reinterpret_cast<float*>(id + a.N);           // [64]
-    A = reinterpret_cast<int*>(qrow + 64);               // [N] left stoppers, [N] right stoppers, block scratch
-    Bd = A + a.N;
-    red = Bd + a.N;                                      // [16 + 2*256 + 2]
-  } else {
-    // rows too long for an LDS image (N > ~10 100): the four row-sized arrays live in the caller's tie_work, one 16 N-byte
-    // slice per block (the host checked that it is there); __syncthreads() orders a block's global accesses as well
-    val = reinterpret_cast<float*>(gwork);
-    id = reinterpret_cast<int*>(val + a.N);
-    A = id + a.N;
-    Bd = A + a.N;
-    qrow = reinterpret_cast<float*>(smem);
-    red = reinterpret_cast<int*>(qrow + 64);
-  }
-  {
-    const int b = row / a.N, qi = row - b * a.N;
-    const float* xb = a.x + (size_t)b * a.N * a.ldx;
-    __syncthreads();
-    if (a.C == 64 && threadIdx.x < 64) qrow[threadIdx.x] = xb[(size_t)qi * a.ldx + threadIdx.x];
-    __syncthreads();
-    for (int j = threadIdx.x; j < a.N; j += blockDim.x) {
-      float d;
-      if (a.C == 64) {
-        const float* c = xb + (size_t)j * a.ldx;
-        f32x4 cr[16];
-#pragma unroll
-        for (int m = 0; m < 16; ++m) cr[m] = ld4(c + 4 * m);    // the whole row in flight, then the chain
-        float acc = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < 64; ++kk) acc = fmaf(cr[kk >> 2][kk & 3], qrow[kk], acc);
-        acc = fmaf(-0.5f * a.sq[(size_t)b * a.N + j], 1.f, acc);
-        d = 2.f * acc - a.sq[(size_t)b * a.N + qi];
-      } else {
-        const f32x4 qv = ld4(xb + (size_t)qi * a.ldx), cv = ld4(xb + (size_t)j * a.ldx);
-        const float dot = fmaf(qv[2], cv[2], fmaf(qv[1], cv[1], qv[0] * cv[0]));
-        d = (2.f * dot - cv[3]) - qv[3];
-      }
-      val[j] = d == d ? d : VCR_NEG_INF;                 // NaN (a non-finite point): below everything, as the main kernels filter it;
-      id[j] = j;                                         // the ports' stoppers and the block partition need a total order
-    }
-    __syncthreads();
-    PairArr q{val, id};
-    const int K = a.k + 1;                               // topk(k + 1)
-    const bool use_heap = (long)K * 64 <= a.N;
-    if (!use_heap) {
-      // std::nth_element(K-1): the partition passes over long ranges run on the whole block (see below); the tail
-      // (range <= 24, depth exhaustion, final insertion sort) is finished by thread 0 with the sequential port.
-      int first = 0, last = a.N, depth = 0;
-      for (int m = a.N; m > 1; m >>= 1) ++depth;
-      depth *= 2;
-      while (last - first > 24 && depth > 0) {
-        --depth;
-        const int cut = tb_partition_parallel(q, first, last, A, Bd, red);
-        if (cut <= K - 1) first = cut; else last = cut;
-      }
-      if (threadIdx.x == 0) tb_nth_element(q, first, last, K - 1, depth);
-    } else if (threadIdx.x < 64) {
-      // std::partial_sort branch ((k+1)*64 <= N): heap across the lanes of wave 0
-      LaneHeap h;
-      const int lane = threadIdx.x;
-      tb_heap_select_wave(val, a.N, K, h, lane);
-      if (lane < K) { val[lane] = h.hv; id[lane] = h.hid; }           // the kept set, like the sequential port leaves it
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      // rank 0 = the largest of the K kept.  Shared by two or more of them (duplicate points ...): the one Tensor.topk
-      // returns FIRST, i.e. position 0 after what ATen does next with the selected entries -- std::sort of the first K - 1
-      // (the nth_element branch; the K-th is not above any of them) or partial_sort's __sort_heap of the K-entry heap
-      int best = 0, nbest = 1;
-      for (int i = 1; i < K; ++i) {
-        if (val[i] > val[best]) { best = i; nbest = 1; }
-        else if (val[i] == val[best]) ++nbest;
-      }
-      if (nbest > 1) {
-        if (use_heap) tb_sort_heap(q, 0, K); else tb_sort(q, 0, K - 1, red);
-        best = 0;
-      }
-      int32_t* o = a.idx + (size_t)row * a.k;
-      int w = 0;
-      for (int i = 0; i < K; ++i)
-        if (i != best) o[w++] = id[i];
-    }
-  }
-}
-
-__device__ __forceinline__ void tiebreak_body(const vcr_knn_args& a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  // rows too long for an LDS image (N > ~10 100): the four row-sized arrays live in the caller's tie_work, one 16 N-byte
-  // slice per block (the host checked that it is there); __syncthreads() orders a block's global accesses as well
-  unsigned char* gwork = tiebreak_lds(a.N) <= TB_LDS_MAX ? nullptr
-                                                         : reinterpret_cast<unsigned char*>(a.tie_work) + (size_t)blockIdx.x * 16 * a.N;
-  const int count = min(a.tie_scratch[0], a.tie_cap);
-  for (int t = blockIdx.x; t < count; t += gridDim.x) tiebreak_row(a, a.tie_scratch[1 + t], smem, gwork);
-}
-
-__global__ __launch_bounds__(256) void knn_tiebreak_kernel(vcr_knn_args a) { tiebreak_body(a); }
-// the replays of two kNN launches in one launch (blockIdx.y picks the launch): one latency instead of two
-__global__ __launch_bounds__(256) void knn_tiebreak2_kernel(vcr_knn_args a, vcr_knn_args b) {
-  if (blockIdx.y == 0) tiebreak_body(a); else tiebreak_body(b);
 }
 
 }  // namespace
