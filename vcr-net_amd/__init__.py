@@ -11,7 +11,7 @@ the repository root).
 """
 from . import weights, synth  # noqa: F401
 
-__all__ = ["weights", "synth", "farthest_point_sample", "register_sampled"]
+__all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "score_registration"]
 
 
 def __getattr__(name):
@@ -22,4 +22,7 @@ def __getattr__(name):
     if name == "register_sampled":
         from .module import register_sampled
         return register_sampled
+    if name == "score_registration":
+        from .score import score_registration
+        return score_registration
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -10,6 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libvcr_hip.so")
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")
+PUBLIC_HEADERS = [os.path.join(INCLUDE, f) for f in ("vcr_hip.h", "vcr_hip_score.h")]   # what every object's digest takes in
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off"]   # no silent a*b+c fusion: the kernels spell out every fmaf they want
@@ -25,7 +27,7 @@ def sources_sha16() -> str:
     import hashlib
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h")))
-    files.append(os.path.join(os.path.dirname(HERE), "include", "vcr_hip.h"))
+    files += PUBLIC_HEADERS
     for f in files:
         h.update(os.path.basename(f).encode())
         with open(f, "rb") as fh:
@@ -80,7 +82,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     GPU box -- may reorder mtimes, and must neither trigger a rebuild there nor hide one that is needed."""
     os.makedirs(OBJ, exist_ok=True)
     hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
-    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "vcr_hip.h"))
+    hdrs += PUBLIC_HEADERS
     flags = " ".join(FLAGS)
     jobs, want = [], {}
     for src in sources():
@@ -142,7 +144,7 @@ def build_host_example() -> str:
     root = os.path.dirname(HERE)
     src = os.path.join(root, "examples", "host_cpp", "forward_host.cpp")
     exe = os.path.join(root, "examples", "host_cpp", "forward_host")
-    want = _digest([src, os.path.join(root, "include", "vcr_hip.h")], _recorded(os.path.join(OBJ, "libvcr_hip.so.sha")) or "")
+    want = _digest([src, PUBLIC_HEADERS[0]], _recorded(os.path.join(OBJ, "libvcr_hip.so.sha")) or "")
     if os.path.exists(exe) and _recorded(exe + ".sha") == want:
         return exe
     r = subprocess.run([HIPCC, "-O2", "-std=c++17", "-I" + os.path.join(root, "include"), src, "-L" + HERE, "-lvcr_hip",

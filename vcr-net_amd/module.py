@@ -737,13 +737,15 @@ def vcrnetIter(net, src, tgt, iter=1):
     return srcK, corrK, R_f, t_f, R_ba, t_ba
 
 
-def register_sampled(net, src, tgt, npoint, iter=1, start=None):
+def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None):
     """Register two clouds of ANY size: src [B,3,Ns] and tgt [B,3,Nt] (Ns != Nt allowed, each up to 131 072 points) are reduced
     to ``npoint`` points each by farthest-point sampling on the device (two vcr_fps_f32 launches, the reference's
     farthest_point_sample index for index), and ``vcrnetIter(net, src_s, tgt_s, iter)`` runs on the sampled clouds.  The
     samples are subsets of the clouds, so the pose returned is the pose of the full clouds.
     ``start``: None = the reference's start (the point farthest from the barycentre), or a pair (start_src, start_tgt) of
-    int [B] first points.  Returns (srcK, src_corrK, R_ab, t_ab, R_ba, t_ba, idx_src, idx_tgt), idx_* int64 [B, npoint]."""
+    int [B] first points.  Returns (srcK, src_corrK, R_ab, t_ab, R_ba, t_ba, idx_src, idx_tgt), idx_* int64 [B, npoint].
+    ``score``: a distance -- the tuple gets a ninth element, ``score_registration(src, tgt, R_ab, t_ab, max_dist=score)``: how
+    well the returned pose fits the FULL clouds (fitness, inlier_rmse, inliers)."""
     for name, x in (("src", src), ("tgt", tgt)):
         if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != 3:
             raise native.VcrHipError(f"register_sampled: {name} must be a [B, 3, N] point cloud, got "
@@ -757,4 +759,8 @@ def register_sampled(net, src, tgt, npoint, iter=1, start=None):
     s_src, s_tgt = (None, None) if start is None else start
     idx_s, src_s = native.fps(src.float(), npoint, start=s_src)
     idx_t, tgt_s = native.fps(tgt.float(), npoint, start=s_tgt)
-    return tuple(vcrnetIter(net, src_s, tgt_s, iter)) + (idx_s.long(), idx_t.long())
+    out = tuple(vcrnetIter(net, src_s, tgt_s, iter)) + (idx_s.long(), idx_t.long())
+    if score is not None:
+        from .score import score_registration
+        out += (score_registration(src, tgt, out[2], out[3], max_dist=score),)
+    return out

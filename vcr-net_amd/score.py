@@ -1,0 +1,154 @@
+"""ctypes binding of include/vcr_hip_score.h and the Python API on top of it: scoring a registration on the FULL clouds
+ -- per source point the nearest target point, per cloud fitness and inlier RMSE (Open3D's
+evaluate_registration) -- by vcr_nn_score_f32, without an Ns x Nt matrix.
+
+The header extends include/vcr_hip.h without touching it, and so does this module for ``native``: its own STRUCTS / SIGNATURES
+maps, in the same shape, applied once to ``native.lib()`` on first use.  No CPU fallback, as everywhere."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import torch
+
+from . import native
+from .native import VcrHipError, f32p, ptr
+
+MAX_N = 131072
+QUERIES_PER_LANE = (1, 2, 4)
+MAX_SPLITS = 128
+
+
+i32p = f64p = C.c_void_p                                   # device pointers travel as integers, like f32p: the names say what they point to
+
+
+class NnScoreArgs(native._Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("src", f32p), ("tgt", f32p), ("B", C.c_int), ("Ns", C.c_int), ("Nt", C.c_int),
+                ("R", f32p), ("t", f32p), ("max_dist", C.c_float), ("nn_idx", i32p), ("nn_d2", f32p), ("inliers", i32p),
+                ("sum_d2", f64p), ("fitness", f32p), ("rmse", f32p), ("variant", C.c_int)]
+
+
+STRUCTS = {"vcr_nn_score_args": NnScoreArgs}
+
+_int, _size, _vp = C.c_int, C.c_size_t, C.c_void_p
+_intp = C.POINTER(C.c_int)
+
+# name -> (restype, [argtypes]): the prototypes of include/vcr_hip_score.h (tests/test_nnscore_cpu.py holds them to it)
+SIGNATURES = {
+    "vcr_nn_score_workspace_bytes": (_size, [C.POINTER(NnScoreArgs), _int]),
+    "vcr_nn_score_f32": (_int, [C.POINTER(NnScoreArgs), _vp, _size, _vp]),
+    "vcr_nn_score_form": (_int, [C.POINTER(NnScoreArgs), _int, _intp, _intp]),
+}
+
+_typed = False
+
+
+def lib() -> C.CDLL:
+    """native.lib() with this module's entry points typed (once)."""
+    global _typed
+    L = native.lib()
+    if not _typed:
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
+        _typed = True
+    return L
+
+
+def variant(queries_per_lane: int = 0, target_splits: int = 0) -> int:
+    """vcr_nn_score_args.variant that forces a form (VCR_NN_SCORE_VARIANT): 0 leaves that half to the plan."""
+    return int(queries_per_lane) | (int(target_splits) << 8)
+
+
+def nn_score_form(B, Ns, Nt, cu_count=256, variant=0):
+    """vcr_nn_score_form (host only with an explicit cu_count): (source points per lane, target splits, workspace bytes)
+    vcr_nn_score_f32 would run [B,3,Ns] against [B,3,Nt] with on a device of cu_count compute units."""
+    a = NnScoreArgs(0x1000, 0x2000, B, Ns, Nt, None, None, 0.0, None, None, None, None, 0x3000, 0x4000, variant)   # (never dereferenced on the host)
+    q, s = C.c_int(0), C.c_int(0)
+    native.check(lib().vcr_nn_score_form(C.byref(a), cu_count, C.byref(q), C.byref(s)), "vcr_nn_score_form")
+    return q.value, s.value, lib().vcr_nn_score_workspace_bytes(C.byref(a), cu_count)
+
+
+def _cloud(name, x):
+    if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != 3:
+        raise VcrHipError(f"score_registration: {name} must be a [B, 3, N] point cloud, got "
+                          f"{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+
+
+@native._guarded
+def nn_score(src, tgt, R=None, t=None, max_dist=0.0, variant=0, want_nn=True, guard=0, prefill=None):
+    """vcr_nn_score_f32 on src [B,3,Ns], tgt [B,3,Nt] (device, fp32) under the pose (R [B,3,3], t [B,3]; both None = identity)
+    -> dict of nn_idx int32 [B,Ns], nn_d2 [B,Ns] (want_nn), inliers int32 [B], sum_d2 float64 [B], fitness, rmse float32 [B].
+    guard / prefill (tests): every output is a view of a buffer with `guard` more elements behind it, all of it filled with the
+    byte `prefill` before the launch; the buffers come back under "_raw"."""
+    _cloud("src", src)
+    _cloud("tgt", tgt)
+    if src.shape[0] != tgt.shape[0]:
+        raise VcrHipError(f"score_registration: src and tgt must hold the same number of clouds, got {src.shape[0]} "
+                          f"and {tgt.shape[0]}")
+    if not (src.is_cuda and tgt.is_cuda):
+        raise VcrHipError("score_registration runs on the MI355X HIP path only; move the clouds to cuda "
+                          "(there is no CPU fallback by design)")
+    if (R is None) != (t is None):
+        raise VcrHipError("score_registration: give both R and t, or neither (the identity)")
+    max_dist = float(max_dist)
+    if not (math.isfinite(max_dist) and max_dist >= 0.0):
+        raise VcrHipError(f"score_registration: max_dist must be finite and >= 0, got {max_dist}")
+    dev = native.same_device(src, tgt, R, t)
+    B, _, Ns = src.shape
+    Nt = tgt.shape[2]
+    src, tgt = src.contiguous().float(), tgt.contiguous().float()
+    if R is not None:
+        if tuple(R.shape) != (B, 3, 3) or tuple(t.shape) != (B, 3):
+            raise VcrHipError(f"score_registration: R must be [B, 3, 3] and t [B, 3] with B = {B}, got {tuple(R.shape)} "
+                              f"and {tuple(t.shape)}")
+        R, t = R.contiguous().float(), t.contiguous().float()
+
+    raw = {}
+
+    def out(name, n, dtype):
+        buf = torch.empty(n + guard, dtype=dtype, device=dev)
+        if prefill is not None:
+            buf.view(torch.uint8).fill_(prefill)
+        raw[name] = buf
+        return buf[:n]
+    o = {}
+    if want_nn:
+        o["nn_idx"], o["nn_d2"] = out("nn_idx", B * Ns, torch.int32).view(B, Ns), out("nn_d2", B * Ns, torch.float32).view(B, Ns)
+    o["inliers"], o["sum_d2"] = out("inliers", B, torch.int32), out("sum_d2", B, torch.float64)
+    o["fitness"], o["rmse"] = out("fitness", B, torch.float32), out("rmse", B, torch.float32)
+    a = NnScoreArgs(ptr(src), ptr(tgt), B, Ns, Nt, ptr(R), ptr(t), max_dist, ptr(o.get("nn_idx")), ptr(o.get("nn_d2")),
+                    ptr(o["inliers"]), ptr(o["sum_d2"]), ptr(o["fitness"]), ptr(o["rmse"]), int(variant))
+    L = lib()
+    need = L.vcr_nn_score_workspace_bytes(C.byref(a), 0)
+    if need == 0:                                            # refused: let the entry point say why
+        native.check(L.vcr_nn_score_f32(C.byref(a), None, 0, native.stream_ptr()), "vcr_nn_score_f32")
+        raise VcrHipError("vcr_nn_score_workspace_bytes: 0 for arguments vcr_nn_score_f32 accepts")
+    ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
+    off = (-ws.data_ptr()) % 256
+    native.check(L.vcr_nn_score_f32(C.byref(a), ws.data_ptr() + off, need, native.stream_ptr()), "vcr_nn_score_f32")
+    if guard or prefill is not None:
+        o["_raw"] = raw
+    return o
+
+
+def score_registration(src, tgt, R=None, t=None, max_dist=0.0, symmetric=False, want_nn=False):
+    """How good is the pose (R, t) for the FULL clouds?  src [B,3,Ns], tgt [B,3,Nt] (Ns != Nt allowed, each up to 131 072
+    points; device tensors): every source point is moved by the pose and matched to its nearest target point.  Returns a dict:
+      fitness      float32 [B]   the fraction of source points within max_dist of the target
+      inlier_rmse  float32 [B]   the RMS distance of those points to their neighbours (0 without inliers)
+      inliers      int32 [B]     their number
+      nn_idx, nn_d2 (want_nn)    int64 / float32 [B,Ns]: the neighbour (the lowest index among equals; -1 when no target point
+                                 is at a finite distance) and the squared distance to it
+    symmetric: also tgt -> src under the inverse pose (native.pose_step's R_ba, t_ba), as fitness_ba, inlier_rmse_ba,
+    inliers_ba.  R = t = None: the identity."""
+    f = nn_score(src, tgt, R, t, max_dist, want_nn=want_nn)
+    res = {"fitness": f["fitness"], "inlier_rmse": f["rmse"], "inliers": f["inliers"]}
+    if want_nn:
+        res["nn_idx"], res["nn_d2"] = f["nn_idx"].long(), f["nn_d2"]
+    if symmetric:
+        R_ba = t_ba = None
+        if R is not None:
+            _, _, _, R_ba, t_ba = native.pose_step(R, t)
+        g = nn_score(tgt, src, R_ba, t_ba, max_dist, want_nn=False)
+        res.update(fitness_ba=g["fitness"], inlier_rmse_ba=g["rmse"], inliers_ba=g["inliers"])
+    return res
