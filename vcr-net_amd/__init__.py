@@ -11,7 +11,7 @@ the repository root).
 """
 from . import weights, synth  # noqa: F401
 
-__all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "score_registration"]
+__all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "score_registration", "refine_registration"]
 
 
 def __getattr__(name):
@@ -25,4 +25,7 @@ def __getattr__(name):
     if name == "score_registration":
         from .score import score_registration
         return score_registration
+    if name == "refine_registration":
+        from .refine import refine_registration
+        return refine_registration
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libvcr_hip.so")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
-PUBLIC_HEADERS = [os.path.join(INCLUDE, f) for f in ("vcr_hip.h", "vcr_hip_score.h")]   # what every object's digest takes in
+PUBLIC_HEADERS = [os.path.join(INCLUDE, f) for f in ("vcr_hip.h", "vcr_hip_score.h", "vcr_hip_refine.h")]   # what every object's digest takes in
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off"]   # no silent a*b+c fusion: the kernels spell out every fmaf they want

@@ -1,0 +1,162 @@
+"""ctypes binding of include/vcr_hip_refine.h and the Python API on top of it: refining a registration on the FULL clouds
+ -- a trimmed point-to-point ICP (Open3D's registration_icp with a correspondence-distance cap) by
+vcr_refine_f32: per cloud its own stop, on the device, no host synchronisation inside the loop.
+
+Like ``score``, the header extends include/vcr_hip.h without touching it and this module keeps its own STRUCTS / SIGNATURES
+maps, applied once to ``native.lib()`` on first use.  No CPU fallback, as everywhere."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import torch
+
+from . import native
+from .native import VcrHipError, f32p, ptr
+from .score import i32p, f64p, variant  # noqa: F401  (the search's forms are the score's: VCR_NN_SCORE_VARIANT)
+
+MAX_ITERATIONS = 4096
+
+
+class RefineArgs(native._Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("src", f32p), ("tgt", f32p), ("B", C.c_int), ("Ns", C.c_int), ("Nt", C.c_int),
+                ("R", f32p), ("t", f32p), ("max_dist", C.c_float), ("max_iterations", C.c_int), ("rel_fitness", C.c_float),
+                ("rel_rmse", C.c_float), ("R_out", f32p), ("t_out", f32p), ("fitness", f32p), ("rmse", f32p), ("R_ba", f32p),
+                ("t_ba", f32p), ("inliers", i32p), ("sum_d2", f64p), ("iterations", i32p), ("converged", i32p),
+                ("nn_idx", i32p), ("nn_d2", f32p), ("variant", C.c_int)]
+
+
+STRUCTS = {"vcr_refine_args": RefineArgs}
+
+_int, _size, _vp = C.c_int, C.c_size_t, C.c_void_p
+_intp = C.POINTER(C.c_int)
+
+# name -> (restype, [argtypes]): the prototypes of include/vcr_hip_refine.h (tests/test_refine_cpu.py holds them to it)
+SIGNATURES = {
+    "vcr_refine_workspace_bytes": (_size, [C.POINTER(RefineArgs), _int]),
+    "vcr_refine_f32": (_int, [C.POINTER(RefineArgs), _vp, _size, _vp]),
+    "vcr_refine_form": (_int, [C.POINTER(RefineArgs), _int, _intp, _intp]),
+}
+
+_typed = False
+
+
+def lib() -> C.CDLL:
+    """native.lib() with this module's entry points typed (once)."""
+    global _typed
+    L = native.lib()
+    if not _typed:
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
+        _typed = True
+    return L
+
+
+def refine_form(B, Ns, Nt, cu_count=256, variant=0, max_iterations=30):
+    """vcr_refine_form (host only with an explicit cu_count): (source points per lane, target splits, workspace bytes) of the
+    search vcr_refine_f32 would run for [B,3,Ns] against [B,3,Nt] on a device of cu_count compute units."""
+    a = RefineArgs(src=0x1000, tgt=0x2000, B=B, Ns=Ns, Nt=Nt, max_iterations=max_iterations, R_out=0x3000, t_out=0x4000,
+                   fitness=0x5000, rmse=0x6000, variant=variant)                  # (never dereferenced on the host)
+    q, s = C.c_int(0), C.c_int(0)
+    native.check(lib().vcr_refine_form(C.byref(a), cu_count, C.byref(q), C.byref(s)), "vcr_refine_form")
+    return q.value, s.value, lib().vcr_refine_workspace_bytes(C.byref(a), cu_count)
+
+
+def _cloud(name, x):
+    if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != 3:
+        raise VcrHipError(f"refine_registration: {name} must be a [B, 3, N] point cloud, got "
+                          f"{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+
+
+def _threshold(name, v):
+    v = float(v)
+    if not (math.isfinite(v) and v >= 0.0):
+        raise VcrHipError(f"refine_registration: {name} must be finite and >= 0, got {v}")
+    return v
+
+
+@native._guarded
+def refine(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6, variant=0, want_nn=True,
+           guard=0, prefill=None):
+    """vcr_refine_f32 on src [B,3,Ns], tgt [B,3,Nt] (device, fp32) from the pose (R [B,3,3], t [B,3]; both None = identity)
+    -> dict of R [B,3,3], t [B,3], R_ba, t_ba, fitness, rmse float32 [B], inliers, iterations, converged int32 [B], sum_d2
+    float64 [B], nn_idx int32 / nn_d2 [B,Ns] (want_nn).
+    guard / prefill (tests): every output is a view of a buffer with `guard` more elements behind it, all of it -- and the
+    workspace -- filled with the byte `prefill` before the launch; the buffers come back under "_raw"."""
+    _cloud("src", src)
+    _cloud("tgt", tgt)
+    if src.shape[0] != tgt.shape[0]:
+        raise VcrHipError(f"refine_registration: src and tgt must hold the same number of clouds, got {src.shape[0]} "
+                          f"and {tgt.shape[0]}")
+    if not (src.is_cuda and tgt.is_cuda):
+        raise VcrHipError("refine_registration runs on the MI355X HIP path only; move the clouds to cuda "
+                          "(there is no CPU fallback by design)")
+    if (R is None) != (t is None):
+        raise VcrHipError("refine_registration: give both R and t, or neither (the identity)")
+    max_dist = _threshold("max_dist", max_dist)
+    rel_fitness, rel_rmse = _threshold("rel_fitness", rel_fitness), _threshold("rel_rmse", rel_rmse)
+    max_iterations = int(max_iterations)
+    if max_iterations < 0:
+        raise VcrHipError(f"refine_registration: max_iterations must be >= 0, got {max_iterations}")
+    dev = native.same_device(src, tgt, R, t)
+    B, _, Ns = src.shape
+    Nt = tgt.shape[2]
+    src, tgt = src.contiguous().float(), tgt.contiguous().float()
+    if R is not None:
+        if tuple(R.shape) != (B, 3, 3) or tuple(t.shape) != (B, 3):
+            raise VcrHipError(f"refine_registration: R must be [B, 3, 3] and t [B, 3] with B = {B}, got {tuple(R.shape)} "
+                              f"and {tuple(t.shape)}")
+        R, t = R.contiguous().float(), t.contiguous().float()
+
+    raw = {}
+
+    def out(name, n, dtype):
+        buf = torch.empty(n + guard, dtype=dtype, device=dev)
+        if prefill is not None:
+            buf.view(torch.uint8).fill_(prefill)
+        raw[name] = buf
+        return buf[:n]
+    o = {"R": out("R", B * 9, torch.float32).view(B, 3, 3), "t": out("t", B * 3, torch.float32).view(B, 3),
+         "R_ba": out("R_ba", B * 9, torch.float32).view(B, 3, 3), "t_ba": out("t_ba", B * 3, torch.float32).view(B, 3),
+         "fitness": out("fitness", B, torch.float32), "rmse": out("rmse", B, torch.float32),
+         "inliers": out("inliers", B, torch.int32), "sum_d2": out("sum_d2", B, torch.float64),
+         "iterations": out("iterations", B, torch.int32), "converged": out("converged", B, torch.int32)}
+    if want_nn:
+        o["nn_idx"], o["nn_d2"] = out("nn_idx", B * Ns, torch.int32).view(B, Ns), out("nn_d2", B * Ns, torch.float32).view(B, Ns)
+    a = RefineArgs(ptr(src), ptr(tgt), B, Ns, Nt, ptr(R), ptr(t), max_dist, max_iterations, rel_fitness, rel_rmse,
+                   ptr(o["R"]), ptr(o["t"]), ptr(o["fitness"]), ptr(o["rmse"]), ptr(o["R_ba"]), ptr(o["t_ba"]),
+                   ptr(o["inliers"]), ptr(o["sum_d2"]), ptr(o["iterations"]), ptr(o["converged"]),
+                   ptr(o.get("nn_idx")), ptr(o.get("nn_d2")), int(variant))
+    L = lib()
+    need = L.vcr_refine_workspace_bytes(C.byref(a), 0)
+    if need == 0:                                            # refused: let the entry point say why
+        native.check(L.vcr_refine_f32(C.byref(a), None, 0, native.stream_ptr()), "vcr_refine_f32")
+        raise VcrHipError("vcr_refine_workspace_bytes: 0 for arguments vcr_refine_f32 accepts")
+    ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
+    if prefill is not None:
+        ws.fill_(prefill)
+    off = (-ws.data_ptr()) % 256
+    native.check(L.vcr_refine_f32(C.byref(a), ws.data_ptr() + off, need, native.stream_ptr()), "vcr_refine_f32")
+    if guard or prefill is not None:
+        o["_raw"] = raw
+    return o
+
+
+def refine_registration(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6,
+                        want_nn=False):
+    """Improve the pose (R, t) on the FULL clouds: src [B,3,Ns], tgt [B,3,Nt] (Ns != Nt allowed, each up to 131 072 points;
+    device tensors).  A point-to-point ICP: every round matches each moved source point to its nearest target point, keeps the
+    pairs within max_dist and solves the best rigid update for them; a cloud stops on its own when fitness and inlier RMSE
+    both change by less than rel_fitness / rel_rmse, when fewer than three pairs are left, or after max_iterations updates.
+    Returns a dict:
+      R, t           float32 [B,3,3], [B,3]   the refined pose (src -> tgt);  R_ba, t_ba: its inverse
+      fitness, inlier_rmse, inliers           of the refined pose, exactly score_registration(src, tgt, R, t, max_dist)'s
+      iterations     int32 [B]                updates applied;  converged  int32 [B]: 1 = stopped by the rel_* test
+      nn_idx, nn_d2 (want_nn)                 int64 / float32 [B,Ns], as score_registration's
+    R = t = None: start from the identity."""
+    f = refine(src, tgt, R, t, max_dist, max_iterations, rel_fitness, rel_rmse, want_nn=want_nn)
+    res = {"R": f["R"], "t": f["t"], "R_ba": f["R_ba"], "t_ba": f["t_ba"], "fitness": f["fitness"], "inlier_rmse": f["rmse"],
+           "inliers": f["inliers"], "iterations": f["iterations"], "converged": f["converged"]}
+    if want_nn:
+        res["nn_idx"], res["nn_d2"] = f["nn_idx"].long(), f["nn_d2"]
+    return res
