@@ -11,7 +11,8 @@ the repository root).
 """
 from . import weights, synth  # noqa: F401
 
-__all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "score_registration", "refine_registration"]
+__all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "score_registration", "refine_registration",
+           "estimate_normals"]
 
 
 def __getattr__(name):
@@ -28,4 +29,7 @@ def __getattr__(name):
     if name == "refine_registration":
         from .refine import refine_registration
         return refine_registration
+    if name == "estimate_normals":
+        from .plane import estimate_normals
+        return estimate_normals
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

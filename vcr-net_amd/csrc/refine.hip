@@ -2,7 +2,8 @@
 // every round is nnscore's scan (nn_scan.h: one text, gated per cloud here) followed by two kernels of this file.
 //
 // One launch up front and three per round, max_iterations + 1 rounds, all enqueued at once (no host synchronisation):
-//   refine_init_kernel    one lane per cloud: the fp64 pose, its fp32 rounding in R_out / t_out (what the scan reads), live = 1.
+//   refine_init_kernel    (refine_state.h, shared with refine_plane.hip) one lane per cloud: the fp64 pose, its fp32 rounding in
+//                         R_out / t_out (what the scan reads), live = 1.
 //   nn_scan_kernel<Q>     as vcr_nn_score_f32 runs it, under (R_out, t_out).
 //   refine_merge_kernel   one lane per source point: folds the S candidates as nn_merge_kernel does (nn_fold), writes nn_idx /
 //                         nn_d2, recomputes the moved point (the scan's expression), gathers the neighbour and reduces its 256
@@ -13,50 +14,13 @@
 // live[b] is the gate: a workgroup of any of the three whose cloud has stopped returns before it loads anything else, and the
 // cloud's outputs stay as its last evaluation wrote them -- a cloud's result does not depend on its batch.  The reductions'
 // geometry depends on Ns alone, so every form of the scan returns the same bits.  No atomics.
-#include "nn_scan.h"
+#include "refine_state.h"
 #include "svd3.h"
-#include "../../include/vcr_hip_refine.h"
 
 namespace {
 
 constexpr int RF_VALUES = 17;                              // sum_d2, count, S_p[3], S_q[3], S_pq[9]
 constexpr int RF_CHUNK = 128;                              // partials the per-cloud kernel stages in LDS at a time (17 KB)
-
-struct RfState {                                           // per cloud, in the workspace
-  double* pose;                                            // [B][12]: R row-major, t
-  float* prev;                                             // [B][2]: the last evaluation's fitness, rmse
-  int* live; int* iters;                                   // [B] each
-};
-
-// (R_ba, t_ba) of the fp32 pose: pose_step_kernel's expression (forward.hip)
-__device__ void rf_store_pose(const float* r, const float* t, int b, float* R_out, float* t_out, float* R_ba, float* t_ba) {
-  for (int i = 0; i < 9; ++i) R_out[(size_t)b * 9 + i] = r[i];
-  for (int i = 0; i < 3; ++i) t_out[(size_t)b * 3 + i] = t[i];
-  for (int i = 0; i < 3; ++i) {
-    if (R_ba) for (int j = 0; j < 3; ++j) R_ba[(size_t)b * 9 + i * 3 + j] = r[j * 3 + i];
-    if (t_ba) t_ba[(size_t)b * 3 + i] = -fmaf(r[6 + i], t[2], fmaf(r[3 + i], t[1], r[i] * t[0]));
-  }
-}
-
-struct RfInit {
-  const float* R; const float* t; int B;
-  RfState st;
-  float* R_out; float* t_out; float* R_ba; float* t_ba;
-};
-
-__global__ __launch_bounds__(NN_BLOCK) void refine_init_kernel(RfInit p) {
-  const int b = blockIdx.x * NN_BLOCK + threadIdx.x;
-  if (b >= p.B) return;
-  float r[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, t[3] = {0.f, 0.f, 0.f};
-  if (p.R) {
-    for (int i = 0; i < 9; ++i) r[i] = p.R[(size_t)b * 9 + i];
-    for (int i = 0; i < 3; ++i) t[i] = p.t[(size_t)b * 3 + i];
-  }
-  for (int i = 0; i < 9; ++i) p.st.pose[(size_t)b * 12 + i] = (double)r[i];
-  for (int i = 0; i < 3; ++i) p.st.pose[(size_t)b * 12 + 9 + i] = (double)t[i];
-  rf_store_pose(r, t, b, p.R_out, p.t_out, p.R_ba, p.t_ba);
-  p.st.live[b] = 1; p.st.iters[b] = 0;                     // (prev is written by round 0 before round 1 reads it)
-}
 
 struct RfMerge {
   const float* part_d2; const int* part_idx;
@@ -214,38 +178,7 @@ __global__ __launch_bounds__(NN_BLOCK) void refine_cloud_kernel(RfCloud p) {
   rf_store_pose(rf, tf, b, p.R_out, p.t_out, p.R_ba, p.t_ba);
 }
 
-// nn_plan on the search this call runs (under R_out / t_out), the arguments of its own checked first, and the workspace:
-// the scan's candidates | the partials | the per-cloud state
-struct RfPlan {
-  NnPlan nn;
-  size_t part_off, pose_off, prev_off, live_off, iters_off, bytes;
-};
-
 }  // namespace
-
-static int rf_plan(const vcr_refine_args& a, int cu, RfPlan* p) {
-  *p = RfPlan{};
-  if (!a.R_out || !a.t_out || (a.R == nullptr) != (a.t == nullptr) || a.max_iterations < 0) return VCR_EINVAL;
-  const float inf = __builtin_huge_valf();
-  if (!(a.rel_fitness >= 0.f) || a.rel_fitness == inf || !(a.rel_rmse >= 0.f) || a.rel_rmse == inf) return VCR_EINVAL;
-  vcr_nn_score_args s{};
-  s.struct_bytes = (uint32_t)sizeof(s);
-  s.src = a.src; s.tgt = a.tgt; s.B = a.B; s.Ns = a.Ns; s.Nt = a.Nt;
-  s.R = a.R_out; s.t = a.t_out; s.max_dist = a.max_dist;
-  s.nn_idx = a.nn_idx; s.nn_d2 = a.nn_d2; s.inliers = a.inliers; s.sum_d2 = a.sum_d2; s.fitness = a.fitness; s.rmse = a.rmse;
-  s.variant = a.variant;
-  const int e = nn_plan(s, cu, &p->nn);
-  if (e) return e;
-  if (a.max_iterations > VCR_REFINE_MAX_ITERATIONS) return VCR_EUNSUPPORTED;
-  const size_t B = (size_t)a.B;
-  p->part_off = 2 * p->nn.part_bytes;
-  p->pose_off = p->part_off + nn_up(B * p->nn.nblk * RF_VALUES * sizeof(double));
-  p->prev_off = p->pose_off + nn_up(B * 12 * sizeof(double));
-  p->live_off = p->prev_off + nn_up(B * 2 * sizeof(float));
-  p->iters_off = p->live_off + nn_up(B * sizeof(int));
-  p->bytes = p->iters_off + nn_up(B * sizeof(int));
-  return VCR_OK;
-}
 
 static int rf_take(const vcr_refine_args* user, vcr_refine_args* mine) {
   return vcr_take_args(user, mine, offsetof(vcr_refine_args, R_ba));
@@ -255,7 +188,7 @@ extern "C" int vcr_refine_form(const vcr_refine_args* ua, int cu_count, int* que
   vcr_refine_args a;
   RfPlan p;
   if (rf_take(ua, &a) || cu_count < 0) return VCR_EINVAL;
-  const int e = rf_plan(a, cu_count ? cu_count : vcr_cu_count(), &p);
+  const int e = rf_plan(a, cu_count ? cu_count : vcr_cu_count(), RF_VALUES, &p);
   if (e) return e;
   if (queries_per_lane) *queries_per_lane = p.nn.Q;
   if (target_splits) *target_splits = p.nn.S;
@@ -266,7 +199,7 @@ extern "C" size_t vcr_refine_workspace_bytes(const vcr_refine_args* ua, int cu_c
   vcr_refine_args a;
   RfPlan p;
   if (rf_take(ua, &a) || cu_count < 0) return 0;
-  return rf_plan(a, cu_count ? cu_count : vcr_cu_count(), &p) ? 0 : p.bytes;
+  return rf_plan(a, cu_count ? cu_count : vcr_cu_count(), RF_VALUES, &p) ? 0 : p.bytes;
 }
 
 extern "C" int vcr_refine_f32(const vcr_refine_args* ua, void* workspace, size_t workspace_bytes, vcr_stream_t stream) {
@@ -274,11 +207,11 @@ extern "C" int vcr_refine_f32(const vcr_refine_args* ua, void* workspace, size_t
   if (rf_take(ua, &a)) return VCR_EINVAL;
   // the argument checks need no device: only a call that passes them asks for the CU count
   RfPlan p;
-  int e = rf_plan(a, 1, &p);
+  int e = rf_plan(a, 1, RF_VALUES, &p);
   if (e) return e;
   if (!workspace || (((uintptr_t)workspace) & 15)) return VCR_EINVAL;
   vcr_stream_scope scope_(stream);
-  e = rf_plan(a, vcr_cu_count(), &p);
+  e = rf_plan(a, vcr_cu_count(), RF_VALUES, &p);
   if (e) return e;
   if (workspace_bytes < p.bytes) return VCR_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;

@@ -737,7 +737,7 @@ def vcrnetIter(net, src, tgt, iter=1):
     return srcK, corrK, R_f, t_f, R_ba, t_ba
 
 
-def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refine=None):
+def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refine=None, refine_method="point_to_point"):
     """Register two clouds of ANY size: src [B,3,Ns] and tgt [B,3,Nt] (Ns != Nt allowed, each up to 131 072 points) are reduced
     to ``npoint`` points each by farthest-point sampling on the device (two vcr_fps_f32 launches, the reference's
     farthest_point_sample index for index), and ``vcrnetIter(net, src_s, tgt_s, iter)`` runs on the sampled clouds.  The
@@ -748,7 +748,8 @@ def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refi
     well the returned pose fits the FULL clouds (fitness, inlier_rmse, inliers).
     ``refine``: a distance -- one more element, after the score's if both are given:
     ``refine_registration(src, tgt, R_ab, t_ab, max_dist=refine)``, the pose improved by an ICP on the FULL clouds with that
-    correspondence cap, and its own fitness.  Elements 0-7 are the network's either way."""
+    correspondence cap, and its own fitness.  Elements 0-7 are the network's either way.
+    ``refine_method``: that call's ``method`` -- "point_to_plane" estimates the target's normals and slides along its surface."""
     for name, x in (("src", src), ("tgt", tgt)):
         if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != 3:
             raise native.VcrHipError(f"register_sampled: {name} must be a [B, 3, N] point cloud, got "
@@ -768,5 +769,5 @@ def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refi
         out += (score_registration(src, tgt, out[2], out[3], max_dist=score),)
     if refine is not None:
         from .refine import refine_registration
-        out += (refine_registration(src, tgt, out[2], out[3], max_dist=refine),)
+        out += (refine_registration(src, tgt, out[2], out[3], max_dist=refine, method=refine_method),)
     return out

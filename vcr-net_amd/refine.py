@@ -77,12 +77,14 @@ def _threshold(name, v):
 
 @native._guarded
 def refine(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6, variant=0, want_nn=True,
-           guard=0, prefill=None):
+           guard=0, prefill=None, tgt_normals=None):
     """vcr_refine_f32 on src [B,3,Ns], tgt [B,3,Nt] (device, fp32) from the pose (R [B,3,3], t [B,3]; both None = identity)
     -> dict of R [B,3,3], t [B,3], R_ba, t_ba, fitness, rmse float32 [B], inliers, iterations, converged int32 [B], sum_d2
     float64 [B], nn_idx int32 / nn_d2 [B,Ns] (want_nn).
     guard / prefill (tests): every output is a view of a buffer with `guard` more elements behind it, all of it -- and the
-    workspace -- filled with the byte `prefill` before the launch; the buffers come back under "_raw"."""
+    workspace -- filled with the byte `prefill` before the launch; the buffers come back under "_raw".
+    tgt_normals [B,3,Nt]: vcr_refine_plane_f32 instead -- the same loop with the point-to-plane fit (plane.refine_plane checks
+    them and calls this)."""
     _cloud("src", src)
     _cloud("tgt", tgt)
     if src.shape[0] != tgt.shape[0]:
@@ -123,38 +125,63 @@ def refine(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitnes
          "iterations": out("iterations", B, torch.int32), "converged": out("converged", B, torch.int32)}
     if want_nn:
         o["nn_idx"], o["nn_d2"] = out("nn_idx", B * Ns, torch.int32).view(B, Ns), out("nn_d2", B * Ns, torch.float32).view(B, Ns)
-    a = RefineArgs(ptr(src), ptr(tgt), B, Ns, Nt, ptr(R), ptr(t), max_dist, max_iterations, rel_fitness, rel_rmse,
-                   ptr(o["R"]), ptr(o["t"]), ptr(o["fitness"]), ptr(o["rmse"]), ptr(o["R_ba"]), ptr(o["t_ba"]),
-                   ptr(o["inliers"]), ptr(o["sum_d2"]), ptr(o["iterations"]), ptr(o["converged"]),
-                   ptr(o.get("nn_idx")), ptr(o.get("nn_d2")), int(variant))
-    L = lib()
-    need = L.vcr_refine_workspace_bytes(C.byref(a), 0)
+    Args, L, entry = RefineArgs, lib(), "vcr_refine"
+    if tgt_normals is not None:
+        from . import plane
+        Args, L, entry = plane.RefinePlaneArgs, plane.lib(), "vcr_refine_plane"
+    f32, workspace_bytes = getattr(L, entry + "_f32"), getattr(L, entry + "_workspace_bytes")
+    a = Args(ptr(src), ptr(tgt), B, Ns, Nt, ptr(R), ptr(t), max_dist, max_iterations, rel_fitness, rel_rmse,
+             ptr(o["R"]), ptr(o["t"]), ptr(o["fitness"]), ptr(o["rmse"]), ptr(o["R_ba"]), ptr(o["t_ba"]),
+             ptr(o["inliers"]), ptr(o["sum_d2"]), ptr(o["iterations"]), ptr(o["converged"]),
+             ptr(o.get("nn_idx")), ptr(o.get("nn_d2")), int(variant))
+    if tgt_normals is not None:
+        a.tgt_normals = ptr(tgt_normals)
+    need = workspace_bytes(C.byref(a), 0)
     if need == 0:                                            # refused: let the entry point say why
-        native.check(L.vcr_refine_f32(C.byref(a), None, 0, native.stream_ptr()), "vcr_refine_f32")
-        raise VcrHipError("vcr_refine_workspace_bytes: 0 for arguments vcr_refine_f32 accepts")
+        native.check(f32(C.byref(a), None, 0, native.stream_ptr()), entry + "_f32")
+        raise VcrHipError(f"{entry}_workspace_bytes: 0 for arguments {entry}_f32 accepts")
     ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
     if prefill is not None:
         ws.fill_(prefill)
     off = (-ws.data_ptr()) % 256
-    native.check(L.vcr_refine_f32(C.byref(a), ws.data_ptr() + off, need, native.stream_ptr()), "vcr_refine_f32")
+    native.check(f32(C.byref(a), ws.data_ptr() + off, need, native.stream_ptr()), entry + "_f32")
     if guard or prefill is not None:
         o["_raw"] = raw
     return o
 
 
+METHODS = ("point_to_point", "point_to_plane")
+
+
 def refine_registration(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6,
-                        want_nn=False):
+                        want_nn=False, method="point_to_point", tgt_normals=None, normal_k=20):
     """Improve the pose (R, t) on the FULL clouds: src [B,3,Ns], tgt [B,3,Nt] (Ns != Nt allowed, each up to 131 072 points;
-    device tensors).  A point-to-point ICP: every round matches each moved source point to its nearest target point, keeps the
-    pairs within max_dist and solves the best rigid update for them; a cloud stops on its own when fitness and inlier RMSE
-    both change by less than rel_fitness / rel_rmse, when fewer than three pairs are left, or after max_iterations updates.
+    device tensors).  An ICP: every round matches each moved source point to its nearest target point, keeps the pairs within
+    max_dist and solves the best rigid update for them; a cloud stops on its own when fitness and inlier RMSE both change by
+    less than rel_fitness / rel_rmse, when too few pairs are left, or after max_iterations updates.
+    method "point_to_point" (the default): the update pulls every point onto its neighbour (at least three pairs).
+    method "point_to_plane": the update pulls every point onto its neighbour's tangent plane, so the clouds may slide along the
+    surface -- fewer rounds where they are different samplings of one surface (at least six pairs, and normals that span:
+    a flat target stops at once).  tgt_normals [B,3,Nt] are the target's unit normals; None: estimate_normals(tgt, normal_k).
     Returns a dict:
       R, t           float32 [B,3,3], [B,3]   the refined pose (src -> tgt);  R_ba, t_ba: its inverse
       fitness, inlier_rmse, inliers           of the refined pose, exactly score_registration(src, tgt, R, t, max_dist)'s
       iterations     int32 [B]                updates applied;  converged  int32 [B]: 1 = stopped by the rel_* test
       nn_idx, nn_d2 (want_nn)                 int64 / float32 [B,Ns], as score_registration's
     R = t = None: start from the identity."""
-    f = refine(src, tgt, R, t, max_dist, max_iterations, rel_fitness, rel_rmse, want_nn=want_nn)
+    if method not in METHODS:
+        raise VcrHipError(f"refine_registration: method must be one of {METHODS}, got {method!r}")
+    if method == "point_to_plane":
+        from . import plane
+        _cloud("src", src)
+        _cloud("tgt", tgt)
+        if tgt_normals is None:
+            tgt_normals = plane.estimate_normals(tgt, normal_k)
+        f = plane.refine_plane(src, tgt, tgt_normals, R, t, max_dist, max_iterations, rel_fitness, rel_rmse, want_nn=want_nn)
+    else:
+        if tgt_normals is not None:
+            raise VcrHipError("refine_registration: tgt_normals are read by method='point_to_plane' only")
+        f = refine(src, tgt, R, t, max_dist, max_iterations, rel_fitness, rel_rmse, want_nn=want_nn)
     res = {"R": f["R"], "t": f["t"], "R_ba": f["R_ba"], "t_ba": f["t_ba"], "fitness": f["fitness"], "inlier_rmse": f["rmse"],
            "inliers": f["inliers"], "iterations": f["iterations"], "converged": f["converged"]}
     if want_nn:
