@@ -7,6 +7,8 @@ import re
 
 import pytest
 
+from boundary import prototypes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "vcr_hip.h")
 INTERNAL_HEADER = os.path.join(ROOT, "vcr-net_amd", "csrc", "vcr_internal.h")
@@ -23,28 +25,6 @@ def lib():
 def declared_symbols(header=None):
     src = open(header or HEADER).read()
     return sorted(set(re.findall(r"\b(vcr_[a-z0-9_]+)\s*\(", src)))
-
-
-def prototypes(header):
-    """{name: (return type, [parameter types])} of every `ret vcr_name(params);` of a header, comments and preprocessor lines
-    stripped; a type is its base name with one '*' per level of indirection, `const` and parameter names dropped."""
-    src = re.sub(r"/\*.*?\*/", " ", open(header).read(), flags=re.S)
-    src = re.sub(r"//[^\n]*", " ", src)
-    src = re.sub(r"^\s*#.*$", " ", src, flags=re.M)
-
-    def ctype(text, named):
-        tok = text.replace("*", " * ").split()
-        if named and len(tok) >= 2 and tok[-1] != "*":       # a type is one word or ends in '*': what follows is the name
-            tok = tok[:-1]
-        tok = [t for t in tok if t != "const"]
-        assert len(tok) >= 1 and all(t == "*" for t in tok[1:]), text
-        return tok[0] + "*" * (len(tok) - 1)
-    out = {}
-    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\**)\s*\b(vcr_\w+)\s*\(([^()]*)\)\s*;", src):
-        assert name not in out, name
-        params = [] if params.strip() in ("", "void") else params.split(",")
-        out[name] = (ctype(ret, False), [ctype(p, True) for p in params])
-    return out
 
 
 def test_header_symbols_exported(lib):

@@ -4,13 +4,12 @@ picks on 256 CUs (DESIGN.md section 4.8's table), and the numpy restatement (tes
 written as a plain double loop."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import boundary
 import nnscore_restated as nr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,51 +25,9 @@ def lib():
     return score.lib()
 
 
-def _stripped(header):
-    src = re.sub(r"/\*.*?\*/", " ", open(header).read(), flags=re.S)
-    src = re.sub(r"//[^\n]*", " ", src)
-    return re.sub(r"^\s*#.*$", " ", src, flags=re.M)
-
-
-def prototypes(header):
-    """{name: (return type, [parameter types])} of every `ret vcr_name(params);`: a type is its base name with one '*' per
-    level of indirection, `const` and parameter names dropped."""
-    def ctype(text, named):
-        tok = text.replace("*", " * ").split()
-        if named and len(tok) >= 2 and tok[-1] != "*":
-            tok = tok[:-1]
-        tok = [t for t in tok if t != "const"]
-        assert len(tok) >= 1 and all(t == "*" for t in tok[1:]), text
-        return tok[0] + "*" * (len(tok) - 1)
-    out = {}
-    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\**)\s*\b(vcr_\w+)\s*\(([^()]*)\)\s*;", _stripped(header)):
-        assert name not in out, name
-        params = [] if params.strip() in ("", "void") else params.split(",")
-        out[name] = (ctype(ret, False), [ctype(p, True) for p in params])
-    return out
-
-
 def test_signatures_match_the_header_and_the_library_exports_them(lib):
     from vcrnet_amd import score
-    scalars = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "long": ctypes.c_long, "float": ctypes.c_float}
-    protos = prototypes(HEADER)
-    assert set(protos) == set(score.SIGNATURES) == {"vcr_nn_score_workspace_bytes", "vcr_nn_score_f32", "vcr_nn_score_form"}
-    for name, (ret, params) in protos.items():
-        res, args = score.SIGNATURES[name]
-        assert res is scalars[ret], (name, ret, res)
-        assert len(args) == len(params), (name, params, args)
-        for i, (c, t) in enumerate(zip(params, args)):
-            if c in scalars:
-                assert t is scalars[c], (name, i, c, t)
-            elif c.startswith("vcr_") and c != "vcr_stream_t":
-                assert c.endswith("*") and not c.endswith("**"), (name, i, c)
-                assert t is ctypes.POINTER(score.STRUCTS[c[:-1]]), (name, i, c, t)
-            else:
-                assert c == "vcr_stream_t" or c.endswith("*"), (name, i, c)
-                assert t is ctypes.c_void_p or issubclass(t, ctypes._Pointer), (name, i, c, t)
-        assert hasattr(lib, name), f"{name} declared in include/vcr_hip_score.h but not exported"
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
+    boundary.check_signatures(HEADER, score, lib, {"vcr_nn_score_workspace_bytes", "vcr_nn_score_f32", "vcr_nn_score_form"})
 
 
 def test_the_main_boundary_is_where_it_was(lib):
@@ -86,23 +43,7 @@ def test_the_main_boundary_is_where_it_was(lib):
 def test_args_match_the_c_layout(tmp_path):
     import vcrnet_amd  # noqa: F401
     from vcrnet_amd import score
-    hdr = _stripped(HEADER)
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(void) {']
-    expect = []
-    for cname, ct in score.STRUCTS.items():
-        assert re.search(r"typedef struct[^{]*\{[^{}]*\}\s*%s;" % cname, hdr), cname
-        lines.append(f'printf("%zu\\n", sizeof({cname}));')
-        expect.append((cname, "sizeof", ctypes.sizeof(ct)))
-        for fname, _ in ct._fields_:
-            lines.append(f'printf("%zu\\n", offsetof({cname}, {fname}));')
-            expect.append((cname, fname, getattr(ct, fname).offset))
-    lines.append("return 0; }")
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == [e for _, _, e in expect], list(zip(expect, got))
+    boundary.check_layout(HEADER, score, tmp_path)
     assert score.NnScoreArgs().struct_bytes == ctypes.sizeof(score.NnScoreArgs)
 
 

@@ -4,15 +4,14 @@ the resource remarks of the new kernels, and the numpy restatement (tests/plane_
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import boundary
 import plane_restated as pr
 import refine_restated as rr
-from test_nnscore_cpu import _stripped, prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "vcr_hip_plane.h")
@@ -30,26 +29,8 @@ def lib():
 
 def test_signatures_match_the_header_and_the_library_exports_them(lib):
     from vcrnet_amd import plane
-    scalars = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "long": ctypes.c_long, "float": ctypes.c_float}
-    protos = prototypes(HEADER)
-    assert set(protos) == set(plane.SIGNATURES) == {"vcr_normals_f32", "vcr_refine_plane_workspace_bytes", "vcr_refine_plane_f32",
-                                                    "vcr_refine_plane_form"}
-    for name, (ret, params) in protos.items():
-        res, args = plane.SIGNATURES[name]
-        assert res is scalars[ret], (name, ret, res)
-        assert len(args) == len(params), (name, params, args)
-        for i, (c, t) in enumerate(zip(params, args)):
-            if c in scalars:
-                assert t is scalars[c], (name, i, c, t)
-            elif c.startswith("vcr_") and c != "vcr_stream_t":
-                assert c.endswith("*") and not c.endswith("**"), (name, i, c)
-                assert t is ctypes.POINTER(plane.STRUCTS[c[:-1]]), (name, i, c, t)
-            else:
-                assert c == "vcr_stream_t" or c.endswith("*"), (name, i, c)
-                assert t is ctypes.c_void_p or issubclass(t, ctypes._Pointer), (name, i, c, t)
-        assert hasattr(lib, name), f"{name} declared in include/vcr_hip_plane.h but not exported"
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
+    boundary.check_signatures(HEADER, plane, lib, {"vcr_normals_f32", "vcr_refine_plane_workspace_bytes", "vcr_refine_plane_f32",
+                                                   "vcr_refine_plane_form"})
 
 
 def test_the_other_boundaries_are_where_they_were(lib, monkeypatch):
@@ -60,9 +41,9 @@ def test_the_other_boundaries_are_where_they_were(lib, monkeypatch):
     for header in ("vcr_hip.h", "vcr_hip_score.h", "vcr_hip_refine.h"):
         text = open(os.path.join(ROOT, "include", header)).read()
         assert "vcr_normals" not in text and "vcr_refine_plane" not in text
-    assert [os.path.basename(h) for h in build.PLANE_HEADERS] == ["vcr_hip_plane.h"]
+    assert os.path.basename(build.PUBLIC_HEADERS[-1]) == "vcr_hip_plane.h"
     full = build.sources_sha16()                              # the digests take the new header in
-    monkeypatch.setattr(build, "PLANE_HEADERS", [])
+    monkeypatch.setattr(build, "PUBLIC_HEADERS", build.PUBLIC_HEADERS[:-1])
     assert build.sources_sha16() != full
     monkeypatch.undo()
     assert int(re.search(r"#define\s+VCR_NORMALS_MAX_K\s+(\d+)", open(HEADER).read()).group(1)) == plane.MAX_K == 62
@@ -74,25 +55,7 @@ def test_the_other_boundaries_are_where_they_were(lib, monkeypatch):
 def test_args_match_the_c_layout(tmp_path):
     import vcrnet_amd  # noqa: F401
     from vcrnet_amd import plane
-    hdr = _stripped(HEADER)
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(void) {']
-    expect = []
-    for cname, ct in plane.STRUCTS.items():
-        assert re.search(r"typedef struct[^{]*\{[^{}]*\}\s*%s;" % cname, hdr), cname
-        lines.append(f'printf("%zu\\n", sizeof({cname}));')
-        expect.append((cname, "sizeof", ctypes.sizeof(ct)))
-        for fname, _ in ct._fields_:
-            lines.append(f'printf("%zu\\n", offsetof({cname}, {fname}));')
-            expect.append((cname, fname, getattr(ct, fname).offset))
-    lines.append("return 0; }")
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == [e for _, _, e in expect], list(zip(expect, got))
-    for ct in plane.STRUCTS.values():
-        assert ct().struct_bytes == ctypes.sizeof(ct)
+    boundary.check_layout(HEADER, plane, tmp_path)
 
 
 def _nargs(B=2, N=100, k=20):

@@ -5,14 +5,13 @@ planted pose."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import boundary
 import refine_restated as rr
-from test_nnscore_cpu import _stripped, prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "vcr_hip_refine.h")
@@ -29,25 +28,7 @@ def lib():
 
 def test_signatures_match_the_header_and_the_library_exports_them(lib):
     from vcrnet_amd import refine
-    scalars = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "long": ctypes.c_long, "float": ctypes.c_float}
-    protos = prototypes(HEADER)
-    assert set(protos) == set(refine.SIGNATURES) == {"vcr_refine_workspace_bytes", "vcr_refine_f32", "vcr_refine_form"}
-    for name, (ret, params) in protos.items():
-        res, args = refine.SIGNATURES[name]
-        assert res is scalars[ret], (name, ret, res)
-        assert len(args) == len(params), (name, params, args)
-        for i, (c, t) in enumerate(zip(params, args)):
-            if c in scalars:
-                assert t is scalars[c], (name, i, c, t)
-            elif c.startswith("vcr_") and c != "vcr_stream_t":
-                assert c.endswith("*") and not c.endswith("**"), (name, i, c)
-                assert t is ctypes.POINTER(refine.STRUCTS[c[:-1]]), (name, i, c, t)
-            else:
-                assert c == "vcr_stream_t" or c.endswith("*"), (name, i, c)
-                assert t is ctypes.c_void_p or issubclass(t, ctypes._Pointer), (name, i, c, t)
-        assert hasattr(lib, name), f"{name} declared in include/vcr_hip_refine.h but not exported"
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
+    boundary.check_signatures(HEADER, refine, lib, {"vcr_refine_workspace_bytes", "vcr_refine_f32", "vcr_refine_form"})
 
 
 def test_the_other_boundaries_are_where_they_were(lib):
@@ -55,36 +36,21 @@ def test_the_other_boundaries_are_where_they_were(lib):
     new header in."""
     from vcrnet_amd import build, native, refine, score
     assert len(native.PUBLIC) == 51 and len(native.INTERNAL) == 6 and lib.vcr_abi_version() == native.ABI_VERSION == 27
-    assert len(score.SIGNATURES) == 3 and len(prototypes(os.path.join(ROOT, "include", "vcr_hip_score.h"))) == 3
+    assert len(score.SIGNATURES) == 3 and len(boundary.prototypes(os.path.join(ROOT, "include", "vcr_hip_score.h"))) == 3
     for other in (native, score):
         assert not set(refine.SIGNATURES) & set(other.SIGNATURES) and not set(refine.STRUCTS) & set(other.STRUCTS)
     for header in ("vcr_hip.h", "vcr_hip_score.h"):
         assert "vcr_refine" not in open(os.path.join(ROOT, "include", header)).read()
     assert refine.RefineArgs.__module__ == refine.__name__
-    assert [os.path.basename(h) for h in build.PUBLIC_HEADERS] == ["vcr_hip.h", "vcr_hip_score.h", "vcr_hip_refine.h"]
+    assert [os.path.basename(h) for h in build.PUBLIC_HEADERS] == ["vcr_hip.h", "vcr_hip_score.h", "vcr_hip_refine.h",
+                                                                      "vcr_hip_plane.h"]
     assert int(re.search(r"#define\s+VCR_REFINE_MAX_ITERATIONS\s+(\d+)", open(HEADER).read()).group(1)) == refine.MAX_ITERATIONS
 
 
 def test_args_match_the_c_layout(tmp_path):
     import vcrnet_amd  # noqa: F401
     from vcrnet_amd import refine
-    hdr = _stripped(HEADER)
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(void) {']
-    expect = []
-    for cname, ct in refine.STRUCTS.items():
-        assert re.search(r"typedef struct[^{]*\{[^{}]*\}\s*%s;" % cname, hdr), cname
-        lines.append(f'printf("%zu\\n", sizeof({cname}));')
-        expect.append((cname, "sizeof", ctypes.sizeof(ct)))
-        for fname, _ in ct._fields_:
-            lines.append(f'printf("%zu\\n", offsetof({cname}, {fname}));')
-            expect.append((cname, fname, getattr(ct, fname).offset))
-    lines.append("return 0; }")
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == [e for _, _, e in expect], list(zip(expect, got))
+    boundary.check_layout(HEADER, refine, tmp_path)
     assert refine.RefineArgs().struct_bytes == ctypes.sizeof(refine.RefineArgs)
 
 

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import torch
 
-from . import native, refine
+from . import extension, native, refine
 from .native import VcrHipError, f32p, ptr
 from .score import i32p
 
@@ -27,30 +27,11 @@ class RefinePlaneArgs(native._Sized):
 
 STRUCTS = {"vcr_normals_args": NormalsArgs, "vcr_refine_plane_args": RefinePlaneArgs}
 
-_int, _size, _vp = C.c_int, C.c_size_t, C.c_void_p
-_intp = C.POINTER(C.c_int)
-
 # name -> (restype, [argtypes]): the prototypes of include/vcr_hip_plane.h (tests/test_plane_cpu.py holds them to it)
-SIGNATURES = {
-    "vcr_normals_f32": (_int, [C.POINTER(NormalsArgs), _vp]),
-    "vcr_refine_plane_workspace_bytes": (_size, [C.POINTER(RefinePlaneArgs), _int]),
-    "vcr_refine_plane_f32": (_int, [C.POINTER(RefinePlaneArgs), _vp, _size, _vp]),
-    "vcr_refine_plane_form": (_int, [C.POINTER(RefinePlaneArgs), _int, _intp, _intp]),
-}
+SIGNATURES = {"vcr_normals_f32": (C.c_int, [C.POINTER(NormalsArgs), C.c_void_p]),
+              **extension.workspace_signatures("vcr_refine_plane", RefinePlaneArgs)}
 
-_typed = False
-
-
-def lib() -> C.CDLL:
-    """native.lib() with this module's entry points typed (once)."""
-    global _typed
-    L = native.lib()
-    if not _typed:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _typed = True
-    return L
+lib = extension.typed_lib(SIGNATURES)                      # native.lib() with this module's entry points typed (once)
 
 
 def refine_plane_form(B, Ns, Nt, cu_count=256, variant=0, max_iterations=30):
@@ -58,9 +39,7 @@ def refine_plane_form(B, Ns, Nt, cu_count=256, variant=0, max_iterations=30):
     as refine.refine_form."""
     a = RefinePlaneArgs(src=0x1000, tgt=0x2000, B=B, Ns=Ns, Nt=Nt, max_iterations=max_iterations, R_out=0x3000, t_out=0x4000,
                         fitness=0x5000, rmse=0x6000, variant=variant, tgt_normals=0x7000)   # (never dereferenced on the host)
-    q, s = C.c_int(0), C.c_int(0)
-    native.check(lib().vcr_refine_plane_form(C.byref(a), cu_count, C.byref(q), C.byref(s)), "vcr_refine_plane_form")
-    return q.value, s.value, lib().vcr_refine_plane_workspace_bytes(C.byref(a), cu_count)
+    return extension.form(lib(), "vcr_refine_plane", a, cu_count)
 
 
 @native._guarded
@@ -80,16 +59,9 @@ def normals(xyz4, idx, viewpoint=None, want_curvature=True, guard=0, prefill=Non
         if tuple(viewpoint.shape) != (B, 3):
             raise VcrHipError(f"normals: viewpoint must be [B, 3] with B = {B}, got {tuple(viewpoint.shape)}")
         viewpoint = viewpoint.contiguous().float()
-    raw = {}
-
-    def out(name, n):
-        buf = torch.empty(n + guard, dtype=torch.float32, device=dev)
-        if prefill is not None:
-            buf.view(torch.uint8).fill_(prefill)
-        raw[name] = buf
-        return buf[:n]
-    nrm = out("normals", B * 3 * N).view(B, 3, N)
-    cur = out("curvature", B * N).view(B, N) if want_curvature else None
+    out, raw = extension.outputs(dev, guard, prefill)
+    nrm = out("normals", B * 3 * N, torch.float32).view(B, 3, N)
+    cur = out("curvature", B * N, torch.float32).view(B, N) if want_curvature else None
     a = NormalsArgs(ptr(xyz4), ptr(idx), B, N, k, ptr(viewpoint), ptr(nrm), ptr(cur))
     native.check(lib().vcr_normals_f32(C.byref(a), native.stream_ptr()), "vcr_normals_f32")
     return (nrm, cur, raw) if guard or prefill is not None else (nrm, cur)

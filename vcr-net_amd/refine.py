@@ -10,7 +10,7 @@ import ctypes as C
 import math
 import torch
 
-from . import native
+from . import extension, native
 from .native import VcrHipError, f32p, ptr
 from .score import i32p, f64p, variant  # noqa: F401  (the search's forms are the score's: VCR_NN_SCORE_VARIANT)
 
@@ -27,29 +27,10 @@ class RefineArgs(native._Sized):
 
 STRUCTS = {"vcr_refine_args": RefineArgs}
 
-_int, _size, _vp = C.c_int, C.c_size_t, C.c_void_p
-_intp = C.POINTER(C.c_int)
-
 # name -> (restype, [argtypes]): the prototypes of include/vcr_hip_refine.h (tests/test_refine_cpu.py holds them to it)
-SIGNATURES = {
-    "vcr_refine_workspace_bytes": (_size, [C.POINTER(RefineArgs), _int]),
-    "vcr_refine_f32": (_int, [C.POINTER(RefineArgs), _vp, _size, _vp]),
-    "vcr_refine_form": (_int, [C.POINTER(RefineArgs), _int, _intp, _intp]),
-}
+SIGNATURES = extension.workspace_signatures("vcr_refine", RefineArgs)
 
-_typed = False
-
-
-def lib() -> C.CDLL:
-    """native.lib() with this module's entry points typed (once)."""
-    global _typed
-    L = native.lib()
-    if not _typed:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _typed = True
-    return L
+lib = extension.typed_lib(SIGNATURES)                      # native.lib() with this module's entry points typed (once)
 
 
 def refine_form(B, Ns, Nt, cu_count=256, variant=0, max_iterations=30):
@@ -57,15 +38,11 @@ def refine_form(B, Ns, Nt, cu_count=256, variant=0, max_iterations=30):
     search vcr_refine_f32 would run for [B,3,Ns] against [B,3,Nt] on a device of cu_count compute units."""
     a = RefineArgs(src=0x1000, tgt=0x2000, B=B, Ns=Ns, Nt=Nt, max_iterations=max_iterations, R_out=0x3000, t_out=0x4000,
                    fitness=0x5000, rmse=0x6000, variant=variant)                  # (never dereferenced on the host)
-    q, s = C.c_int(0), C.c_int(0)
-    native.check(lib().vcr_refine_form(C.byref(a), cu_count, C.byref(q), C.byref(s)), "vcr_refine_form")
-    return q.value, s.value, lib().vcr_refine_workspace_bytes(C.byref(a), cu_count)
+    return extension.form(lib(), "vcr_refine", a, cu_count)
 
 
 def _cloud(name, x):
-    if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != 3:
-        raise VcrHipError(f"refine_registration: {name} must be a [B, 3, N] point cloud, got "
-                          f"{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+    extension.check_cloud("refine_registration", name, x)
 
 
 def _threshold(name, v):
@@ -85,39 +62,14 @@ def refine(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitnes
     workspace -- filled with the byte `prefill` before the launch; the buffers come back under "_raw".
     tgt_normals [B,3,Nt]: vcr_refine_plane_f32 instead -- the same loop with the point-to-plane fit (plane.refine_plane checks
     them and calls this)."""
-    _cloud("src", src)
-    _cloud("tgt", tgt)
-    if src.shape[0] != tgt.shape[0]:
-        raise VcrHipError(f"refine_registration: src and tgt must hold the same number of clouds, got {src.shape[0]} "
-                          f"and {tgt.shape[0]}")
-    if not (src.is_cuda and tgt.is_cuda):
-        raise VcrHipError("refine_registration runs on the MI355X HIP path only; move the clouds to cuda "
-                          "(there is no CPU fallback by design)")
-    if (R is None) != (t is None):
-        raise VcrHipError("refine_registration: give both R and t, or neither (the identity)")
+    extension.check_pair("refine_registration", src, tgt, R, t)
     max_dist = _threshold("max_dist", max_dist)
     rel_fitness, rel_rmse = _threshold("rel_fitness", rel_fitness), _threshold("rel_rmse", rel_rmse)
     max_iterations = int(max_iterations)
     if max_iterations < 0:
         raise VcrHipError(f"refine_registration: max_iterations must be >= 0, got {max_iterations}")
-    dev = native.same_device(src, tgt, R, t)
-    B, _, Ns = src.shape
-    Nt = tgt.shape[2]
-    src, tgt = src.contiguous().float(), tgt.contiguous().float()
-    if R is not None:
-        if tuple(R.shape) != (B, 3, 3) or tuple(t.shape) != (B, 3):
-            raise VcrHipError(f"refine_registration: R must be [B, 3, 3] and t [B, 3] with B = {B}, got {tuple(R.shape)} "
-                              f"and {tuple(t.shape)}")
-        R, t = R.contiguous().float(), t.contiguous().float()
-
-    raw = {}
-
-    def out(name, n, dtype):
-        buf = torch.empty(n + guard, dtype=dtype, device=dev)
-        if prefill is not None:
-            buf.view(torch.uint8).fill_(prefill)
-        raw[name] = buf
-        return buf[:n]
+    dev, B, Ns, Nt, src, tgt, R, t = extension.take_pair("refine_registration", src, tgt, R, t)
+    out, raw = extension.outputs(dev, guard, prefill)
     o = {"R": out("R", B * 9, torch.float32).view(B, 3, 3), "t": out("t", B * 3, torch.float32).view(B, 3),
          "R_ba": out("R_ba", B * 9, torch.float32).view(B, 3, 3), "t_ba": out("t_ba", B * 3, torch.float32).view(B, 3),
          "fitness": out("fitness", B, torch.float32), "rmse": out("rmse", B, torch.float32),
@@ -129,22 +81,13 @@ def refine(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitnes
     if tgt_normals is not None:
         from . import plane
         Args, L, entry = plane.RefinePlaneArgs, plane.lib(), "vcr_refine_plane"
-    f32, workspace_bytes = getattr(L, entry + "_f32"), getattr(L, entry + "_workspace_bytes")
     a = Args(ptr(src), ptr(tgt), B, Ns, Nt, ptr(R), ptr(t), max_dist, max_iterations, rel_fitness, rel_rmse,
              ptr(o["R"]), ptr(o["t"]), ptr(o["fitness"]), ptr(o["rmse"]), ptr(o["R_ba"]), ptr(o["t_ba"]),
              ptr(o["inliers"]), ptr(o["sum_d2"]), ptr(o["iterations"]), ptr(o["converged"]),
              ptr(o.get("nn_idx")), ptr(o.get("nn_d2")), int(variant))
     if tgt_normals is not None:
         a.tgt_normals = ptr(tgt_normals)
-    need = workspace_bytes(C.byref(a), 0)
-    if need == 0:                                            # refused: let the entry point say why
-        native.check(f32(C.byref(a), None, 0, native.stream_ptr()), entry + "_f32")
-        raise VcrHipError(f"{entry}_workspace_bytes: 0 for arguments {entry}_f32 accepts")
-    ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
-    if prefill is not None:
-        ws.fill_(prefill)
-    off = (-ws.data_ptr()) % 256
-    native.check(f32(C.byref(a), ws.data_ptr() + off, need, native.stream_ptr()), entry + "_f32")
+    extension.call_with_workspace(L, entry, a, dev, prefill)
     if guard or prefill is not None:
         o["_raw"] = raw
     return o

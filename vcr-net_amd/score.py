@@ -10,7 +10,7 @@ import ctypes as C
 import math
 import torch
 
-from . import native
+from . import extension, native
 from .native import VcrHipError, f32p, ptr
 
 MAX_N = 131072
@@ -29,29 +29,10 @@ class NnScoreArgs(native._Sized):
 
 STRUCTS = {"vcr_nn_score_args": NnScoreArgs}
 
-_int, _size, _vp = C.c_int, C.c_size_t, C.c_void_p
-_intp = C.POINTER(C.c_int)
-
 # name -> (restype, [argtypes]): the prototypes of include/vcr_hip_score.h (tests/test_nnscore_cpu.py holds them to it)
-SIGNATURES = {
-    "vcr_nn_score_workspace_bytes": (_size, [C.POINTER(NnScoreArgs), _int]),
-    "vcr_nn_score_f32": (_int, [C.POINTER(NnScoreArgs), _vp, _size, _vp]),
-    "vcr_nn_score_form": (_int, [C.POINTER(NnScoreArgs), _int, _intp, _intp]),
-}
+SIGNATURES = extension.workspace_signatures("vcr_nn_score", NnScoreArgs)
 
-_typed = False
-
-
-def lib() -> C.CDLL:
-    """native.lib() with this module's entry points typed (once)."""
-    global _typed
-    L = native.lib()
-    if not _typed:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _typed = True
-    return L
+lib = extension.typed_lib(SIGNATURES)                      # native.lib() with this module's entry points typed (once)
 
 
 def variant(queries_per_lane: int = 0, target_splits: int = 0) -> int:
@@ -63,15 +44,7 @@ def nn_score_form(B, Ns, Nt, cu_count=256, variant=0):
     """vcr_nn_score_form (host only with an explicit cu_count): (source points per lane, target splits, workspace bytes)
     vcr_nn_score_f32 would run [B,3,Ns] against [B,3,Nt] with on a device of cu_count compute units."""
     a = NnScoreArgs(0x1000, 0x2000, B, Ns, Nt, None, None, 0.0, None, None, None, None, 0x3000, 0x4000, variant)   # (never dereferenced on the host)
-    q, s = C.c_int(0), C.c_int(0)
-    native.check(lib().vcr_nn_score_form(C.byref(a), cu_count, C.byref(q), C.byref(s)), "vcr_nn_score_form")
-    return q.value, s.value, lib().vcr_nn_score_workspace_bytes(C.byref(a), cu_count)
-
-
-def _cloud(name, x):
-    if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != 3:
-        raise VcrHipError(f"score_registration: {name} must be a [B, 3, N] point cloud, got "
-                          f"{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+    return extension.form(lib(), "vcr_nn_score", a, cu_count)
 
 
 @native._guarded
@@ -80,37 +53,12 @@ def nn_score(src, tgt, R=None, t=None, max_dist=0.0, variant=0, want_nn=True, gu
     -> dict of nn_idx int32 [B,Ns], nn_d2 [B,Ns] (want_nn), inliers int32 [B], sum_d2 float64 [B], fitness, rmse float32 [B].
     guard / prefill (tests): every output is a view of a buffer with `guard` more elements behind it, all of it filled with the
     byte `prefill` before the launch; the buffers come back under "_raw"."""
-    _cloud("src", src)
-    _cloud("tgt", tgt)
-    if src.shape[0] != tgt.shape[0]:
-        raise VcrHipError(f"score_registration: src and tgt must hold the same number of clouds, got {src.shape[0]} "
-                          f"and {tgt.shape[0]}")
-    if not (src.is_cuda and tgt.is_cuda):
-        raise VcrHipError("score_registration runs on the MI355X HIP path only; move the clouds to cuda "
-                          "(there is no CPU fallback by design)")
-    if (R is None) != (t is None):
-        raise VcrHipError("score_registration: give both R and t, or neither (the identity)")
+    extension.check_pair("score_registration", src, tgt, R, t)
     max_dist = float(max_dist)
     if not (math.isfinite(max_dist) and max_dist >= 0.0):
         raise VcrHipError(f"score_registration: max_dist must be finite and >= 0, got {max_dist}")
-    dev = native.same_device(src, tgt, R, t)
-    B, _, Ns = src.shape
-    Nt = tgt.shape[2]
-    src, tgt = src.contiguous().float(), tgt.contiguous().float()
-    if R is not None:
-        if tuple(R.shape) != (B, 3, 3) or tuple(t.shape) != (B, 3):
-            raise VcrHipError(f"score_registration: R must be [B, 3, 3] and t [B, 3] with B = {B}, got {tuple(R.shape)} "
-                              f"and {tuple(t.shape)}")
-        R, t = R.contiguous().float(), t.contiguous().float()
-
-    raw = {}
-
-    def out(name, n, dtype):
-        buf = torch.empty(n + guard, dtype=dtype, device=dev)
-        if prefill is not None:
-            buf.view(torch.uint8).fill_(prefill)
-        raw[name] = buf
-        return buf[:n]
+    dev, B, Ns, Nt, src, tgt, R, t = extension.take_pair("score_registration", src, tgt, R, t)
+    out, raw = extension.outputs(dev, guard, prefill)
     o = {}
     if want_nn:
         o["nn_idx"], o["nn_d2"] = out("nn_idx", B * Ns, torch.int32).view(B, Ns), out("nn_d2", B * Ns, torch.float32).view(B, Ns)
@@ -118,14 +66,7 @@ def nn_score(src, tgt, R=None, t=None, max_dist=0.0, variant=0, want_nn=True, gu
     o["fitness"], o["rmse"] = out("fitness", B, torch.float32), out("rmse", B, torch.float32)
     a = NnScoreArgs(ptr(src), ptr(tgt), B, Ns, Nt, ptr(R), ptr(t), max_dist, ptr(o.get("nn_idx")), ptr(o.get("nn_d2")),
                     ptr(o["inliers"]), ptr(o["sum_d2"]), ptr(o["fitness"]), ptr(o["rmse"]), int(variant))
-    L = lib()
-    need = L.vcr_nn_score_workspace_bytes(C.byref(a), 0)
-    if need == 0:                                            # refused: let the entry point say why
-        native.check(L.vcr_nn_score_f32(C.byref(a), None, 0, native.stream_ptr()), "vcr_nn_score_f32")
-        raise VcrHipError("vcr_nn_score_workspace_bytes: 0 for arguments vcr_nn_score_f32 accepts")
-    ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
-    native.check(L.vcr_nn_score_f32(C.byref(a), ws.data_ptr() + off, need, native.stream_ptr()), "vcr_nn_score_f32")
+    extension.call_with_workspace(lib(), "vcr_nn_score", a, dev)
     if guard or prefill is not None:
         o["_raw"] = raw
     return o
