@@ -12,7 +12,7 @@ the repository root).
 from . import weights, synth  # noqa: F401
 
 __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "score_registration", "refine_registration",
-           "estimate_normals"]
+           "estimate_normals", "voxel_down_sample"]
 
 
 def __getattr__(name):
@@ -32,4 +32,7 @@ def __getattr__(name):
     if name == "estimate_normals":
         from .plane import estimate_normals
         return estimate_normals
+    if name == "voxel_down_sample":
+        from .voxel import voxel_down_sample
+        return voxel_down_sample
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -737,7 +737,8 @@ def vcrnetIter(net, src, tgt, iter=1):
     return srcK, corrK, R_f, t_f, R_ba, t_ba
 
 
-def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refine=None, refine_method="point_to_point"):
+def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refine=None, refine_method="point_to_point",
+                     voxel=None):
     """Register two clouds of ANY size: src [B,3,Ns] and tgt [B,3,Nt] (Ns != Nt allowed, each up to 131 072 points) are reduced
     to ``npoint`` points each by farthest-point sampling on the device (two vcr_fps_f32 launches, the reference's
     farthest_point_sample index for index), and ``vcrnetIter(net, src_s, tgt_s, iter)`` runs on the sampled clouds.  The
@@ -749,7 +750,13 @@ def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refi
     ``refine``: a distance -- one more element, after the score's if both are given:
     ``refine_registration(src, tgt, R_ab, t_ab, max_dist=refine)``, the pose improved by an ICP on the FULL clouds with that
     correspondence cap, and its own fitness.  Elements 0-7 are the network's either way.
-    ``refine_method``: that call's ``method`` -- "point_to_plane" estimates the target's normals and slides along its surface."""
+    ``refine_method``: that call's ``method`` -- "point_to_plane" estimates the target's normals and slides along its surface.
+    ``voxel``: an edge length -- both clouds are first reduced by ``voxel_down_sample(cloud, voxel)``, which leaves every cloud
+    its own number of points: the counts travel to the host (ONE synchronisation), the sampling runs cloud by cloud on
+    [1,3,M_b], the samples are stacked and the network runs once on the batch.  idx_src / idx_tgt and ``start`` then index the
+    DOWN-SAMPLED clouds, ``score`` / ``refine`` run on them cloud by cloud and come back as lists of B results, and a last
+    extra element (src_down, tgt_down) carries the two lists of B tensors [3, M_b] the indices refer to.  A cloud left with
+    fewer than ``npoint`` voxels raises."""
     for name, x in (("src", src), ("tgt", tgt)):
         if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != 3:
             raise native.VcrHipError(f"register_sampled: {name} must be a [B, 3, N] point cloud, got "
@@ -761,6 +768,8 @@ def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refi
         raise native.VcrHipError("register_sampled runs on the MI355X HIP path only; move the clouds to cuda "
                                  "(there is no CPU fallback by design)")
     s_src, s_tgt = (None, None) if start is None else start
+    if voxel is not None:
+        return _register_voxelised(net, src, tgt, npoint, iter, s_src, s_tgt, score, refine, refine_method, voxel)
     idx_s, src_s = native.fps(src.float(), npoint, start=s_src)
     idx_t, tgt_s = native.fps(tgt.float(), npoint, start=s_tgt)
     out = tuple(vcrnetIter(net, src_s, tgt_s, iter)) + (idx_s.long(), idx_t.long())
@@ -771,3 +780,34 @@ def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refi
         from .refine import refine_registration
         out += (refine_registration(src, tgt, out[2], out[3], max_dist=refine, method=refine_method),)
     return out
+
+
+def _register_voxelised(net, src, tgt, npoint, iter, s_src, s_tgt, score, refine, refine_method, voxel):
+    """register_sampled(voxel=h): the clouds down-sampled on the grid, then the same steps cloud by cloud."""
+    from . import voxel as vx
+    ps, cs, _ = vx.voxel_down_sample(src, voxel)
+    pt, ct, _ = vx.voxel_down_sample(tgt, voxel)
+    B = src.shape[0]
+    counts = torch.cat([cs, ct]).cpu()                                         # the one synchronisation
+    src_d, tgt_d = vx.unpad(ps, counts[:B]), vx.unpad(pt, counts[B:])
+    for name, clouds in (("src", src_d), ("tgt", tgt_d)):
+        for b, c in enumerate(clouds):
+            if c.shape[1] < npoint:
+                raise native.VcrHipError(f"register_sampled: {name} cloud {b} has {c.shape[1]} voxels of edge {voxel}, fewer "
+                                         f"than npoint = {npoint}")
+
+    def sample(clouds, start):
+        got = [native.fps(c.unsqueeze(0).contiguous(), npoint, start=None if start is None else start[b:b + 1])
+               for b, c in enumerate(clouds)]
+        return torch.cat([i for i, _ in got]), torch.cat([p for _, p in got])
+    idx_s, src_s = sample(src_d, s_src)
+    idx_t, tgt_s = sample(tgt_d, s_tgt)
+    out = tuple(vcrnetIter(net, src_s, tgt_s, iter)) + (idx_s.long(), idx_t.long())
+    pairs = [(src_d[b].unsqueeze(0), tgt_d[b].unsqueeze(0), out[2][b:b + 1], out[3][b:b + 1]) for b in range(B)]
+    if score is not None:
+        from .score import score_registration
+        out += ([score_registration(s, t, R, tr, max_dist=score) for s, t, R, tr in pairs],)
+    if refine is not None:
+        from .refine import refine_registration
+        out += ([refine_registration(s, t, R, tr, max_dist=refine, method=refine_method) for s, t, R, tr in pairs],)
+    return out + ((src_d, tgt_d),)
