@@ -12,7 +12,7 @@ the repository root).
 from . import weights, synth  # noqa: F401
 
 __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "score_registration", "refine_registration",
-           "estimate_normals", "voxel_down_sample"]
+           "estimate_normals", "voxel_down_sample", "remove_statistical_outlier", "remove_radius_outlier"]
 
 
 def __getattr__(name):
@@ -35,4 +35,7 @@ def __getattr__(name):
     if name == "voxel_down_sample":
         from .voxel import voxel_down_sample
         return voxel_down_sample
+    if name in ("remove_statistical_outlier", "remove_radius_outlier"):
+        from . import outlier
+        return getattr(outlier, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

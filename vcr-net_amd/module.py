@@ -738,7 +738,7 @@ def vcrnetIter(net, src, tgt, iter=1):
 
 
 def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refine=None, refine_method="point_to_point",
-                     voxel=None):
+                     voxel=None, outlier=None):
     """Register two clouds of ANY size: src [B,3,Ns] and tgt [B,3,Nt] (Ns != Nt allowed, each up to 131 072 points) are reduced
     to ``npoint`` points each by farthest-point sampling on the device (two vcr_fps_f32 launches, the reference's
     farthest_point_sample index for index), and ``vcrnetIter(net, src_s, tgt_s, iter)`` runs on the sampled clouds.  The
@@ -756,7 +756,13 @@ def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refi
     [1,3,M_b], the samples are stacked and the network runs once on the batch.  idx_src / idx_tgt and ``start`` then index the
     DOWN-SAMPLED clouds, ``score`` / ``refine`` run on them cloud by cloud and come back as lists of B results, and a last
     extra element (src_down, tgt_down) carries the two lists of B tensors [3, M_b] the indices refer to.  A cloud left with
-    fewer than ``npoint`` voxels raises."""
+    fewer than ``npoint`` voxels raises.
+    ``outlier``: ("statistical", nb_neighbors, std_ratio) or ("radius", nb_points, radius) -- both clouds lose their stray
+    points by ``remove_statistical_outlier`` / ``remove_radius_outlier``, after the voxel grid when ``voxel`` is given and on
+    the raw clouds otherwise.  The filter too leaves every cloud its own size, so the call takes ``voxel``'s cloud-by-cloud
+    route and returns in its form: the filter's counts travel to the host in the same ONE synchronisation as the voxel
+    counts, the indices and the last element refer to the FILTERED clouds, and a cloud left with fewer than ``npoint`` points
+    raises."""
     for name, x in (("src", src), ("tgt", tgt)):
         if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != 3:
             raise native.VcrHipError(f"register_sampled: {name} must be a [B, 3, N] point cloud, got "
@@ -768,8 +774,8 @@ def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refi
         raise native.VcrHipError("register_sampled runs on the MI355X HIP path only; move the clouds to cuda "
                                  "(there is no CPU fallback by design)")
     s_src, s_tgt = (None, None) if start is None else start
-    if voxel is not None:
-        return _register_voxelised(net, src, tgt, npoint, iter, s_src, s_tgt, score, refine, refine_method, voxel)
+    if voxel is not None or outlier is not None:
+        return _register_voxelised(net, src, tgt, npoint, iter, s_src, s_tgt, score, refine, refine_method, voxel, outlier)
     idx_s, src_s = native.fps(src.float(), npoint, start=s_src)
     idx_t, tgt_s = native.fps(tgt.float(), npoint, start=s_tgt)
     out = tuple(vcrnetIter(net, src_s, tgt_s, iter)) + (idx_s.long(), idx_t.long())
@@ -782,18 +788,32 @@ def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refi
     return out
 
 
-def _register_voxelised(net, src, tgt, npoint, iter, s_src, s_tgt, score, refine, refine_method, voxel):
-    """register_sampled(voxel=h): the clouds down-sampled on the grid, then the same steps cloud by cloud."""
+def _register_voxelised(net, src, tgt, npoint, iter, s_src, s_tgt, score, refine, refine_method, voxel, outlier=None):
+    """register_sampled(voxel=h, outlier=spec): the clouds down-sampled on the grid and / or filtered, then the same steps
+    cloud by cloud."""
     from . import voxel as vx
-    ps, cs, _ = vx.voxel_down_sample(src, voxel)
-    pt, ct, _ = vx.voxel_down_sample(tgt, voxel)
     B = src.shape[0]
-    counts = torch.cat([cs, ct]).cpu()                                         # the one synchronisation
-    src_d, tgt_d = vx.unpad(ps, counts[:B]), vx.unpad(pt, counts[B:])
+    ps, pt, counts = src, tgt, []
+    if voxel is not None:
+        ps, cs, _ = vx.voxel_down_sample(src, voxel)
+        pt, ct, _ = vx.voxel_down_sample(tgt, voxel)
+        counts += [cs, ct]
+    if outlier is not None:
+        # on the padded batches: the NaN points behind a cloud's voxels are dropped and seen by nobody (a cloud's result is a
+        # function of its points alone), so no count has to reach the host in between
+        from . import outlier as ol
+        ps, cs, _ = ol.filter_by(outlier, ps)
+        pt, ct, _ = ol.filter_by(outlier, pt)
+        counts += [cs, ct]
+    counts = torch.cat(counts).cpu()                                           # the one synchronisation
+    if voxel is not None and outlier is not None:
+        vx.unpad(src, counts[:B]), vx.unpad(tgt, counts[B:2 * B])              # (a grid too fine raises, as without the filter)
+    src_d, tgt_d = vx.unpad(ps, counts[-2 * B:-B]), vx.unpad(pt, counts[-B:])
+    what = f"voxels of edge {voxel}" if outlier is None else f"points behind the {outlier[0]} outlier filter"
     for name, clouds in (("src", src_d), ("tgt", tgt_d)):
         for b, c in enumerate(clouds):
             if c.shape[1] < npoint:
-                raise native.VcrHipError(f"register_sampled: {name} cloud {b} has {c.shape[1]} voxels of edge {voxel}, fewer "
+                raise native.VcrHipError(f"register_sampled: {name} cloud {b} has {c.shape[1]} {what}, fewer "
                                          f"than npoint = {npoint}")
 
     def sample(clouds, start):
