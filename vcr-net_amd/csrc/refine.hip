@@ -24,8 +24,10 @@ struct PointFit {
   static constexpr int CHUNK = 128;                        // (17 KB of LDS)
   static constexpr int MIN_INLIERS = 3;
   __device__ float gather(int, int, int, int) const { return 0.f; }   // the neighbour is all it reads
+  __device__ float source(int, int, int, int) const { return 0.f; }
   template <class Put>
-  __device__ static void sums(const float* pc, const float* qc, const float*, Put& put) {
+  __device__ void sums(const RfPoint& pt, Put& put) const {
+    const float* pc = pt.pc; const float* qc = pt.qc;
 #pragma unroll
     for (int c = 0; c < 3; ++c) { put(2 + c, (double)pc[c]); put(5 + c, (double)qc[c]); }
 #pragma unroll

@@ -7,10 +7,11 @@
 //                         inliers, J = (p x nrm, nrm), r = p.nrm - q.nrm -- one value at a time through the butterfly, so that
 //                         they are never live together.
 //   plane_cloud_kernel    one workgroup per cloud: the partials in ascending order; then one lane: the round's evaluation, the
-//                         convergence test, A x = -g by Cholesky, R_i = Rz(x2) Ry(x1) Rx(x0), t_i = (x3, x4, x5), the composed
-//                         pose.  A singular system stops the cloud like too few inliers do: the solve runs before the state is
-//                         written.
+//                         convergence test, A x = -g by Cholesky, R_i = Rz(x2) Ry(x1) Rx(x0), t_i = (x3, x4, x5) (both in
+//                         refine_solve6.h, shared with refine_gicp.hip), the composed pose.  A singular system stops the cloud
+//                         like too few inliers do: the solve runs before the state is written.
 #include "refine_round.h"
+#include "refine_solve6.h"
 #include "../../include/vcr_hip_plane.h"
 
 // vcr_refine_args' fields lead vcr_refine_plane_args, in its order and at its offsets: the shared plan reads them as one
@@ -18,8 +19,6 @@ static_assert(offsetof(vcr_refine_plane_args, variant) == offsetof(vcr_refine_ar
               offsetof(vcr_refine_plane_args, tgt_normals) == sizeof(vcr_refine_args), "vcr_refine_plane_args = vcr_refine_args + tgt_normals");
 
 namespace {
-
-constexpr double PL_PIVOT = 1e-12;                         // a Cholesky pivot at or below this times its diagonal entry: singular
 
 struct PlaneFit {
   static constexpr int VALUES = 29;                        // sum_d2, count, A's upper triangle by rows [21], g[6]
@@ -30,8 +29,10 @@ struct PlaneFit {
     const float* nx = nrm + (size_t)b * 3 * Nt;
     return nx[(size_t)c * Nt + bi];
   }
+  __device__ float source(int, int, int, int) const { return 0.f; }   // nothing of the source but the point
   template <class Put>
-  __device__ static void sums(const float* pc, const float* qc, const float* nc, Put& put) {
+  __device__ void sums(const RfPoint& pt, Put& put) const {
+    const float* pc = pt.pc; const float* qc = pt.qc; const float* nc = pt.gc;
     const double p0 = (double)pc[0], p1 = (double)pc[1], p2 = (double)pc[2];
     const double m0 = (double)nc[0], m1 = (double)nc[1], m2 = (double)nc[2];
     double J[6];                                           // products of two fp32 values: exact
@@ -59,49 +60,6 @@ struct PlaneFit {
 
 __global__ __launch_bounds__(NN_BLOCK) void plane_merge_kernel(RfMerge<PlaneFit> p) { rf_merge_body(p); }
 
-// A x = -g for the symmetric A (upper triangle by rows in a21) by Cholesky, fully unrolled: registers only.  false: singular.
-__device__ bool pl_solve(const double* a21, const double* g, double* x) {
-  double A[6][6], L[6][6];
-  int e = 0;
-#pragma unroll
-  for (int r = 0; r < 6; ++r)
-#pragma unroll
-    for (int c = r; c < 6; ++c) { A[r][c] = a21[e]; A[c][r] = a21[e]; ++e; }
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double s = A[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
-    ok = ok && __builtin_isfinite(s) && s > PL_PIVOT * A[j][j];
-    const double d = sqrt(s);
-    L[j][j] = d;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double v = A[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-      L[i][j] = v / d;
-    }
-  }
-  double y[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {                            // L y = -g
-    double v = -g[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
-    y[i] = v / L[i][i];
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {                           // L^T x = y
-    double v = y[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; ++k) v -= L[k][i] * x[k];
-    x[i] = v / L[i][i];
-  }
-  return ok;
-}
-
 __global__ __launch_bounds__(NN_BLOCK) void plane_cloud_kernel(RfCloud p) {
   const int t = threadIdx.x, b = blockIdx.x;
   if (!p.st.live[b]) return;                               // (workgroup-uniform; written only by this workgroup's thread 0, behind the barriers)
@@ -116,14 +74,7 @@ __global__ __launch_bounds__(NN_BLOCK) void plane_cloud_kernel(RfCloud p) {
   const bool step = rf_evaluate(p, b, v, PlaneFit::MIN_INLIERS, true, [&](bool may) { return may && finite ? pl_solve(v + 2, v + 23, x) : may; });
   if (!step) return;
   double Ri[9], ti[3];
-  {
-    double s0, c0, s1, c1, s2, c2;
-    sincos(x[0], &s0, &c0); sincos(x[1], &s1, &c1); sincos(x[2], &s2, &c2);
-    Ri[0] = c2 * c1; Ri[1] = (c2 * s1) * s0 - s2 * c0; Ri[2] = (c2 * s1) * c0 + s2 * s0;
-    Ri[3] = s2 * c1; Ri[4] = (s2 * s1) * s0 + c2 * c0; Ri[5] = (s2 * s1) * c0 - c2 * s0;
-    Ri[6] = -s1;     Ri[7] = c1 * s0;                  Ri[8] = c1 * c0;
-    ti[0] = x[3]; ti[1] = x[4]; ti[2] = x[5];
-  }
+  pl_euler(x, Ri, ti);
   rf_step_pose(p, b, Ri, ti, finite);
 }
 

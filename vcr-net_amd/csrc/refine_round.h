@@ -1,18 +1,21 @@
-// The round of the two refinements on the full clouds, written once: refine.hip (vcr_refine_f32, point to point) and
-// refine_plane.hip (vcr_refine_plane_f32, point to plane) run the same loop and differ in the FIT -- the sums a round
-// accumulates over its inliers and the solve behind them.  Here: the per-cloud state in the workspace and the kernel that
+// The round of the refinements on the full clouds, written once: refine.hip (vcr_refine_f32, point to point),
+// refine_plane.hip (vcr_refine_plane_f32, point to plane) and refine_gicp.hip (vcr_refine_gicp_f32, plane to plane) run the
+// same loop and differ in the FIT -- the sums a round accumulates over its inliers and the solve behind them.  Here: the per-cloud state in the workspace and the kernel that
 // initialises it, the plan (argument checks, form of the search, workspace layout), the body of the merge kernel, the parts of
 // the per-cloud kernel that do not solve (the sum of the partials, the evaluation and the stop test, the composed pose), and
-// the host driver behind the three entry points of either header.
+// the host driver behind the three entry points of each header.
 //
 // A fit is a struct that travels to the merge kernel as RfMerge's last member and supplies
 //   VALUES, CHUNK, MIN_INLIERS   fp64 values per partial (sum_d2 and the count lead), partials the per-cloud kernel stages in
 //                                LDS at a time, inliers a step needs
 //   gather()                     what it reads at the neighbour's index besides the neighbour, a coordinate at a time
-//   sums()                       values 2 ... VALUES - 1 of one source point -- from the moved point, the neighbour and what
-//                                gather() read -- handed to `put` one at a time
+//   source()                     what it reads at the SOURCE point's own index n besides the point, likewise
+//   sums()                       values 2 ... VALUES - 1 of one source point -- from an RfPoint: the moved point, the neighbour,
+//                                what gather() and source() read, the fp32 pose the merge holds and whether the lane is an
+//                                inlier -- handed to `put` one at a time.  A lane that is no inlier must contribute exact zeros:
+//                                its four triples are zero, which is enough for a fit whose every term is a product of them.
 //   Args, take()                 (host) the public argument struct, and the copy of it the call works on
-// The kernels themselves stay in the two .hip files under their own names, as wrappers of the bodies below.
+// The kernels themselves stay in the fits' .hip files under their own names, as wrappers of the bodies below.
 #pragma once
 #include "nn_scan.h"
 #include "../../include/vcr_hip_refine.h"
@@ -57,6 +60,12 @@ __global__ __launch_bounds__(NN_BLOCK) void refine_init_kernel(RfInit p) {
 
 // ---------------------------------------------------------------------------------------------------------------- the merge
 
+struct RfPoint {                                           // one lane of the merge, as a fit's sums() sees it
+  const float* pc; const float* qc; const float* gc; const float* sc;   // [3] each: moved point, neighbour, gather()'s, source()'s
+  const float* R;                                          // [9], the cloud's fp32 pose the scan ran under (read by inliers only)
+  bool in;
+};
+
 template <class Fit>
 struct RfMerge {
   const float* part_d2; const int* part_idx;
@@ -90,17 +99,18 @@ __device__ __forceinline__ void rf_merge_body(const RfMerge<Fit>& p) {
   }
   const bool in = n < Ns && bi >= 0 && best <= p.max_d2;   // nn_merge_kernel's inlier
   // an inlier's d2 is finite, so its moved point and its neighbour are; every other lane contributes exact zeros
-  float pc[3] = {0.f, 0.f, 0.f}, qc[3] = {0.f, 0.f, 0.f}, gc[3] = {0.f, 0.f, 0.f};
-  if (in) {                                                // bi is in [0, Nt): a target index the scan wrote
+  float pc[3] = {0.f, 0.f, 0.f}, qc[3] = {0.f, 0.f, 0.f}, gc[3] = {0.f, 0.f, 0.f}, sc[3] = {0.f, 0.f, 0.f};
+  const float* r = p.R + (size_t)b * 9;
+  if (in) {                                                // bi is in [0, Nt): a target index the scan wrote; n is in [0, Ns)
     const float* sx = p.src + (size_t)b * 3 * Ns;
     const float* tx = p.tgt + (size_t)b * 3 * Nt;
-    const float* r = p.R + (size_t)b * 9;
     const float* tr = p.t + (size_t)b * 3;
     const float x = sx[n], y = sx[Ns + n], z = sx[2 * (size_t)Ns + n];
     for (int c = 0; c < 3; ++c) {                          // the scan's expression, bit for bit
       pc[c] = fmaf(r[3 * c + 2], z, fmaf(r[3 * c + 1], y, r[3 * c] * x)) + tr[c];
       qc[c] = tx[(size_t)c * Nt + bi];
       gc[c] = p.fit.gather(b, Nt, c, bi);
+      sc[c] = p.fit.source(b, Ns, c, n);
     }
   }
   auto put = [&](int e, double v) {                        // one value across the wave, nn_merge_kernel's butterfly
@@ -110,7 +120,7 @@ __device__ __forceinline__ void rf_merge_body(const RfMerge<Fit>& p) {
   };
   put(0, in ? (double)best : 0.);
   put(1, in ? 1. : 0.);
-  Fit::sums(pc, qc, gc, put);
+  p.fit.sums(RfPoint{pc, qc, gc, sc, r, in}, put);
   __syncthreads();
   if (t < Fit::VALUES) {
     double s = red[0][t];

@@ -750,7 +750,8 @@ def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refi
     ``refine``: a distance -- one more element, after the score's if both are given:
     ``refine_registration(src, tgt, R_ab, t_ab, max_dist=refine)``, the pose improved by an ICP on the FULL clouds with that
     correspondence cap, and its own fitness.  Elements 0-7 are the network's either way.
-    ``refine_method``: that call's ``method`` -- "point_to_plane" estimates the target's normals and slides along its surface.
+    ``refine_method``: that call's ``method`` -- "point_to_plane" estimates the target's normals and slides along its surface;
+    "generalized" (plane to plane) estimates the normals of both clouds, on either route below.
     ``voxel``: an edge length -- both clouds are first reduced by ``voxel_down_sample(cloud, voxel)``, which leaves every cloud
     its own number of points: the counts travel to the host (ONE synchronisation), the sampling runs cloud by cloud on
     [1,3,M_b], the samples are stacked and the network runs once on the batch.  idx_src / idx_tgt and ``start`` then index the

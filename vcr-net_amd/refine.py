@@ -54,14 +54,15 @@ def _threshold(name, v):
 
 @native._guarded
 def refine(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6, variant=0, want_nn=True,
-           guard=0, prefill=None, tgt_normals=None):
+           guard=0, prefill=None, tgt_normals=None, src_normals=None, epsilon=None):
     """vcr_refine_f32 on src [B,3,Ns], tgt [B,3,Nt] (device, fp32) from the pose (R [B,3,3], t [B,3]; both None = identity)
     -> dict of R [B,3,3], t [B,3], R_ba, t_ba, fitness, rmse float32 [B], inliers, iterations, converged int32 [B], sum_d2
     float64 [B], nn_idx int32 / nn_d2 [B,Ns] (want_nn).
     guard / prefill (tests): every output is a view of a buffer with `guard` more elements behind it, all of it -- and the
     workspace -- filled with the byte `prefill` before the launch; the buffers come back under "_raw".
     tgt_normals [B,3,Nt]: vcr_refine_plane_f32 instead -- the same loop with the point-to-plane fit (plane.refine_plane checks
-    them and calls this)."""
+    them and calls this).  With src_normals [B,3,Ns] and epsilon as well: vcr_refine_gicp_f32, the plane-to-plane fit
+    (gicp.refine_gicp checks them and calls this)."""
     extension.check_pair("refine_registration", src, tgt, R, t)
     max_dist = _threshold("max_dist", max_dist)
     rel_fitness, rel_rmse = _threshold("rel_fitness", rel_fitness), _threshold("rel_rmse", rel_rmse)
@@ -78,7 +79,10 @@ def refine(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitnes
     if want_nn:
         o["nn_idx"], o["nn_d2"] = out("nn_idx", B * Ns, torch.int32).view(B, Ns), out("nn_d2", B * Ns, torch.float32).view(B, Ns)
     Args, L, entry = RefineArgs, lib(), "vcr_refine"
-    if tgt_normals is not None:
+    if src_normals is not None:
+        from . import gicp
+        Args, L, entry = gicp.RefineGicpArgs, gicp.lib(), "vcr_refine_gicp"
+    elif tgt_normals is not None:
         from . import plane
         Args, L, entry = plane.RefinePlaneArgs, plane.lib(), "vcr_refine_plane"
     a = Args(ptr(src), ptr(tgt), B, Ns, Nt, ptr(R), ptr(t), max_dist, max_iterations, rel_fitness, rel_rmse,
@@ -87,17 +91,19 @@ def refine(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitnes
              ptr(o.get("nn_idx")), ptr(o.get("nn_d2")), int(variant))
     if tgt_normals is not None:
         a.tgt_normals = ptr(tgt_normals)
+    if src_normals is not None:
+        a.src_normals, a.epsilon = ptr(src_normals), epsilon
     extension.call_with_workspace(L, entry, a, dev, prefill)
     if guard or prefill is not None:
         o["_raw"] = raw
     return o
 
 
-METHODS = ("point_to_point", "point_to_plane")
+METHODS = ("point_to_point", "point_to_plane", "generalized")
 
 
 def refine_registration(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6,
-                        want_nn=False, method="point_to_point", tgt_normals=None, normal_k=20):
+                        want_nn=False, method="point_to_point", tgt_normals=None, normal_k=20, src_normals=None, epsilon=1e-3):
     """Improve the pose (R, t) on the FULL clouds: src [B,3,Ns], tgt [B,3,Nt] (Ns != Nt allowed, each up to 131 072 points;
     device tensors).  An ICP: every round matches each moved source point to its nearest target point, keeps the pairs within
     max_dist and solves the best rigid update for them; a cloud stops on its own when fitness and inlier RMSE both change by
@@ -106,6 +112,10 @@ def refine_registration(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=3
     method "point_to_plane": the update pulls every point onto its neighbour's tangent plane, so the clouds may slide along the
     surface -- fewer rounds where they are different samplings of one surface (at least six pairs, and normals that span:
     a flat target stops at once).  tgt_normals [B,3,Nt] are the target's unit normals; None: estimate_normals(tgt, normal_k).
+    method "generalized": plane to plane (generalized ICP) -- every residual is weighed by the local surfaces of BOTH clouds,
+    each point's covariance epsilon along its normal and 1 across it: the fit for two independent samplings of one surface (at
+    least three pairs that are not collinear).  src_normals [B,3,Ns], tgt_normals [B,3,Nt] are unit normals of either sign;
+    None: estimate_normals(cloud, normal_k).  Covariances of the caller's own are not taken.
     Returns a dict:
       R, t           float32 [B,3,3], [B,3]   the refined pose (src -> tgt);  R_ba, t_ba: its inverse
       fitness, inlier_rmse, inliers           of the refined pose, exactly score_registration(src, tgt, R, t, max_dist)'s
@@ -114,7 +124,20 @@ def refine_registration(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=3
     R = t = None: start from the identity."""
     if method not in METHODS:
         raise VcrHipError(f"refine_registration: method must be one of {METHODS}, got {method!r}")
-    if method == "point_to_plane":
+    if method != "generalized" and (src_normals is not None or epsilon != 1e-3):
+        raise VcrHipError("refine_registration: src_normals and epsilon are read by method='generalized' only")
+    if method == "generalized":
+        from . import gicp, plane
+        _cloud("src", src)
+        _cloud("tgt", tgt)
+        epsilon = gicp.check_epsilon(epsilon)
+        if tgt_normals is None:
+            tgt_normals = plane.estimate_normals(tgt, normal_k)
+        if src_normals is None:
+            src_normals = plane.estimate_normals(src, normal_k)
+        f = gicp.refine_gicp(src, tgt, src_normals, tgt_normals, R, t, max_dist, max_iterations, rel_fitness, rel_rmse,
+                             want_nn=want_nn, epsilon=epsilon)
+    elif method == "point_to_plane":
         from . import plane
         _cloud("src", src)
         _cloud("tgt", tgt)
