@@ -12,7 +12,7 @@ the repository root).
 from . import weights, synth  # noqa: F401
 
 __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "score_registration", "refine_registration",
-           "estimate_normals", "voxel_down_sample", "remove_statistical_outlier", "remove_radius_outlier"]
+           "estimate_normals", "voxel_down_sample", "remove_statistical_outlier", "remove_radius_outlier", "compute_fpfh_feature"]
 
 
 def __getattr__(name):
@@ -38,4 +38,7 @@ def __getattr__(name):
     if name in ("remove_statistical_outlier", "remove_radius_outlier"):
         from . import outlier
         return getattr(outlier, name)
+    if name == "compute_fpfh_feature":
+        from .fpfh import compute_fpfh_feature
+        return compute_fpfh_feature
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
