@@ -12,7 +12,8 @@ the repository root).
 from . import weights, synth  # noqa: F401
 
 __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "score_registration", "refine_registration",
-           "estimate_normals", "voxel_down_sample", "remove_statistical_outlier", "remove_radius_outlier", "compute_fpfh_feature"]
+           "estimate_normals", "voxel_down_sample", "remove_statistical_outlier", "remove_radius_outlier", "compute_fpfh_feature",
+           "match_features", "ransac_correspondences", "register_features"]
 
 
 def __getattr__(name):
@@ -41,4 +42,7 @@ def __getattr__(name):
     if name == "compute_fpfh_feature":
         from .fpfh import compute_fpfh_feature
         return compute_fpfh_feature
+    if name in ("match_features", "ransac_correspondences", "register_features"):
+        from . import match
+        return getattr(match, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

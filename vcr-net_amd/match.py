@@ -1,0 +1,208 @@
+"""ctypes binding of include/vcr_hip_match.h and the Python API on top of it: a pose from features
+alone -- the nearest neighbour across two clouds in the 33-d FPFH space (vcr_feat_nn_f32) and a RANSAC over the resulting
+correspondences (vcr_ransac_f32), Open3D's registration_ransac_based_on_feature_matching on the device.
+
+Like ``fpfh``, the header extends include/vcr_hip.h without touching it and this module keeps its own STRUCTS / SIGNATURES maps,
+applied once to ``native.lib()`` on first use.  No CPU fallback, as everywhere."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import torch
+
+from . import extension, native
+from .native import VcrHipError, f32p, ptr
+from .score import i32p, variant  # noqa: F401  (VCR_NN_SCORE_VARIANT's encoding serves vcr_feat_nn_args.variant too)
+
+FEAT_C = 33
+MAX_N = 131072
+MAX_TRIALS = 1 << 20
+QUERIES_PER_LANE = (1, 2, 4)
+MAX_SPLITS = 128
+
+
+class FeatNnArgs(native._Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("a", f32p), ("b", f32p), ("B", C.c_int), ("C", C.c_int), ("Ns", C.c_int),
+                ("Nt", C.c_int), ("nn_idx", i32p), ("nn_d2", f32p), ("mutual", C.c_int), ("rev_idx", i32p), ("variant", C.c_int)]
+
+
+class RansacArgs(native._Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("src", f32p), ("tgt", f32p), ("corr", i32p), ("B", C.c_int), ("Ns", C.c_int),
+                ("Nt", C.c_int), ("max_dist", C.c_float), ("similarity", C.c_float), ("trials", C.c_int), ("seed", C.c_uint32),
+                ("R_out", f32p), ("t_out", f32p), ("best_trial", i32p), ("inliers", i32p), ("pairs", i32p),
+                ("trial_status", i32p), ("trial_picks", i32p), ("trial_pose", f32p), ("trial_inliers", i32p)]
+
+
+STRUCTS = {"vcr_feat_nn_args": FeatNnArgs, "vcr_ransac_args": RansacArgs}
+
+# name -> (restype, [argtypes]): the prototypes of include/vcr_hip_match.h (tests/test_match_cpu.py holds them to it)
+SIGNATURES = dict(extension.workspace_signatures("vcr_feat_nn", FeatNnArgs),
+                  vcr_ransac_workspace_bytes=(C.c_size_t, [C.POINTER(RansacArgs), C.c_int]),
+                  vcr_ransac_f32=(C.c_int, [C.POINTER(RansacArgs), C.c_void_p, C.c_size_t, C.c_void_p]))
+
+lib = extension.typed_lib(SIGNATURES)                      # native.lib() with this module's entry points typed (once)
+
+
+def feat_nn_form(B, Ns, Nt, cu_count=256, variant=0, mutual=False):
+    """vcr_feat_nn_form (host only with an explicit cu_count): (rows of a per lane, splits of b, workspace bytes)
+    vcr_feat_nn_f32 would search [B,33,Ns] in [B,33,Nt] with on a device of cu_count compute units."""
+    a = FeatNnArgs(0x1000, 0x2000, B, FEAT_C, Ns, Nt, 0x3000, None, int(bool(mutual)), None, variant)   # (never dereferenced on the host)
+    return extension.form(lib(), "vcr_feat_nn", a, cu_count)
+
+
+def _features(api, name, x):
+    if not (torch.is_tensor(x) and x.dim() == 3 and x.dtype == torch.float32):
+        raise VcrHipError(f"{api}: {name} must be a float32 [B, {FEAT_C}, N] feature tensor, got "
+                          f"{(tuple(x.shape), x.dtype) if torch.is_tensor(x) else type(x).__name__}")
+    if x.shape[1] != FEAT_C:
+        raise VcrHipError(f"{api}: {name} must have {FEAT_C} channels (compute_fpfh_feature's), got {x.shape[1]}")
+    if x.shape[2] < 1 or x.shape[2] > MAX_N:
+        raise VcrHipError(f"{api}: {name} must hold 1 ... {MAX_N} points, got {x.shape[2]}")
+
+
+def _feature_pair(api, a, b):
+    """Shapes, dtypes and widths first, the device last: every refusal can be met without one."""
+    _features(api, "src_feat", a)
+    _features(api, "tgt_feat", b)
+    if a.shape[0] != b.shape[0]:
+        raise VcrHipError(f"{api}: src_feat and tgt_feat must hold the same number of clouds, got {a.shape[0]} and {b.shape[0]}")
+    if not (a.is_cuda and b.is_cuda):
+        raise VcrHipError(f"{api} runs on the MI355X HIP path only; move the features to cuda (there is no CPU fallback by design)")
+
+
+@native._guarded
+def feat_nn(a, b, mutual=False, want_d2=True, want_rev=False, variant=0, guard=0, prefill=None, api="feat_nn"):
+    """vcr_feat_nn_f32 on a [B,33,Ns], b [B,33,Nt] (device, fp32) -> dict of nn_idx int32 [B,Ns], nn_d2 float32 [B,Ns] (want_d2),
+    rev_idx int32 [B,Nt] (want_rev: the b -> a search).  mutual: nn_idx keeps j only where rev_idx[j] == i, -1 elsewhere.
+    guard / prefill (tests): every output is a view of a buffer with `guard` more elements behind it, all of it -- and the
+    workspace -- filled with the byte `prefill` before the launch; the buffers come back under "_raw"."""
+    _feature_pair(api, a, b)
+    dev = native.same_device(a, b)
+    a, b = a.contiguous(), b.contiguous()
+    B, _, Ns = a.shape
+    Nt = b.shape[2]
+    out, raw = extension.outputs(dev, guard, prefill)
+    o = {"nn_idx": out("nn_idx", B * Ns, torch.int32).view(B, Ns)}
+    if want_d2:
+        o["nn_d2"] = out("nn_d2", B * Ns, torch.float32).view(B, Ns)
+    if want_rev:
+        o["rev_idx"] = out("rev_idx", B * Nt, torch.int32).view(B, Nt)
+    args = FeatNnArgs(ptr(a), ptr(b), B, FEAT_C, Ns, Nt, ptr(o["nn_idx"]), ptr(o.get("nn_d2")), int(bool(mutual)),
+                      ptr(o.get("rev_idx")), int(variant))
+    extension.call_with_workspace(lib(), "vcr_feat_nn", args, dev, prefill)
+    if guard or prefill is not None:
+        o["_raw"] = raw
+    return o
+
+
+def _ransac_checks(api, src, tgt, corr, max_dist, trials, similarity, seed, given_corr=True):
+    """What the RANSAC refuses before any launch -- shapes, dtypes and values first, the device last.  given_corr False: corr is
+    not looked at (register_features computes it)."""
+    extension.check_cloud(api, "src", src)
+    extension.check_cloud(api, "tgt", tgt)
+    if src.shape[0] != tgt.shape[0]:
+        raise VcrHipError(f"{api}: src and tgt must hold the same number of clouds, got {src.shape[0]} and {tgt.shape[0]}")
+    if src.dtype != torch.float32 or tgt.dtype != torch.float32:
+        raise VcrHipError(f"{api}: src and tgt must be float32, got {src.dtype} and {tgt.dtype}")
+    B, _, Ns = src.shape
+    if min(Ns, tgt.shape[2]) < 1 or max(Ns, tgt.shape[2]) > MAX_N:
+        raise VcrHipError(f"{api}: a cloud must hold 1 ... {MAX_N} points, got {Ns} and {tgt.shape[2]}")
+    if given_corr and not (torch.is_tensor(corr) and corr.dtype == torch.int32 and tuple(corr.shape) == (B, Ns)):
+        raise VcrHipError(f"{api}: corr must be int32 [B, Ns] = [{B}, {Ns}] (match_features' result), got "
+                          f"{(tuple(corr.shape), corr.dtype) if torch.is_tensor(corr) else type(corr).__name__}")
+    max_dist, similarity, trials, seed = float(max_dist), float(similarity), int(trials), int(seed)
+    if not (math.isfinite(max_dist) and max_dist >= 0.0):
+        raise VcrHipError(f"{api}: max_dist must be finite and >= 0, got {max_dist}")
+    if not 0.0 <= similarity <= 1.0:
+        raise VcrHipError(f"{api}: similarity must be 0 (no edge-length test) or in (0, 1], got {similarity}")
+    if trials < 1 or trials > MAX_TRIALS:
+        raise VcrHipError(f"{api}: trials must be in [1, {MAX_TRIALS}], got {trials}")
+    if not 0 <= seed < 1 << 32:
+        raise VcrHipError(f"{api}: seed must be in [0, 2^32), got {seed}")
+    if not (src.is_cuda and tgt.is_cuda and (not given_corr or corr.is_cuda)):
+        raise VcrHipError(f"{api} runs on the MI355X HIP path only; move the clouds and corr to cuda "
+                          "(there is no CPU fallback by design)")
+    return max_dist, similarity, trials, seed
+
+
+@native._guarded
+def ransac(src, tgt, corr, max_dist, trials=100000, similarity=0.9, seed=0, want_trials=False, guard=0, prefill=None,
+           api="ransac"):
+    """vcr_ransac_f32 on src [B,3,Ns], tgt [B,3,Nt] (device, fp32) and corr int32 [B,Ns] (the target index per source point;
+    outside [0, Nt): none) -> dict of R [B,3,3], t [B,3], best_trial, inliers, pairs int32 [B]; with want_trials also
+    trial_status int32 [B,T], trial_picks int32 [B,T,3], trial_pose float32 [B,T,12], trial_inliers int32 [B,T].
+    guard / prefill (tests): as ``feat_nn``'s."""
+    max_dist, similarity, T, seed = _ransac_checks(api, src, tgt, corr, max_dist, trials, similarity, seed)
+    dev = native.same_device(src, tgt, corr)
+    src, tgt, corr = src.contiguous(), tgt.contiguous(), corr.contiguous()
+    B, _, Ns = src.shape
+    Nt = tgt.shape[2]
+    out, raw = extension.outputs(dev, guard, prefill)
+    o = {"R": out("R", B * 9, torch.float32).view(B, 3, 3), "t": out("t", B * 3, torch.float32).view(B, 3)}
+    for name in ("best_trial", "inliers", "pairs"):
+        o[name] = out(name, B, torch.int32)
+    if want_trials:
+        o["trial_status"] = out("trial_status", B * T, torch.int32).view(B, T)
+        o["trial_picks"] = out("trial_picks", B * T * 3, torch.int32).view(B, T, 3)
+        o["trial_pose"] = out("trial_pose", B * T * 12, torch.float32).view(B, T, 12)
+        o["trial_inliers"] = out("trial_inliers", B * T, torch.int32).view(B, T)
+    args = RansacArgs(ptr(src), ptr(tgt), ptr(corr), B, Ns, Nt, max_dist, similarity, T, seed, ptr(o["R"]), ptr(o["t"]),
+                      ptr(o["best_trial"]), ptr(o["inliers"]), ptr(o["pairs"]), ptr(o.get("trial_status")),
+                      ptr(o.get("trial_picks")), ptr(o.get("trial_pose")), ptr(o.get("trial_inliers")))
+    extension.call_with_workspace(lib(), "vcr_ransac", args, dev, prefill)
+    if guard or prefill is not None:
+        o["_raw"] = raw
+    return o
+
+
+def match_features(src_feat, tgt_feat, mutual=False, want_d2=False):
+    """For every point of the source its nearest point of the target IN FEATURE SPACE: src_feat [B,33,Ns], tgt_feat [B,33,Nt]
+    (float32 device tensors, compute_fpfh_feature's; Ns != Nt allowed, each up to 131 072) -> int32 [B,Ns], the target index;
+    among equally near target points the lowest index, -1 for a source row without a finite distance.  The distance is the sum
+    of the 33 squared differences in fp32, one fmaf chain in channel order.  mutual: a pair (i, j) is kept only where i is also
+    the nearest source point of j; the others are -1.  want_d2: also the squared feature distances, float32 [B,Ns]."""
+    f = feat_nn(src_feat, tgt_feat, mutual=mutual, want_d2=want_d2, api="match_features")
+    return (f["nn_idx"], f["nn_d2"]) if want_d2 else f["nn_idx"]
+
+
+def ransac_correspondences(src, tgt, corr, max_dist, trials=100000, similarity=0.9, seed=0, want_trials=False):
+    """A pose from correspondences: src [B,3,Ns], tgt [B,3,Nt] (float32 device tensors), corr int32 [B,Ns] (match_features'
+    result: the partner of every source point, -1 = none).  Open3D's registration_ransac_based_on_feature_matching with
+    ransac_n = 3 and its edge-length (similarity; 0 = off) and distance (max_dist) checkers: every trial draws three pairs by
+    a hash of (seed, trial), solves their rigid fit and counts the pairs within max_dist of their partner under it.  ALL
+    `trials` run (no early stop), a trial with a repeated pick is dropped, and the winner is the highest count, the lowest
+    trial among equals -- the result is a function of the inputs and the seed.  Returns a dict:
+      R, t         float32 [B,3,3], [B,3]   the best trial's pose (src -> tgt); the identity when no trial is valid
+      inliers      int32 [B]                its count;  pairs int32 [B]: the number of source points with a partner
+      best_trial   int32 [B]                -1 when no trial is valid
+      trial_status, trial_picks, trial_pose, trial_inliers (want_trials): per trial, as include/vcr_hip_match.h states them."""
+    return ransac(src, tgt, corr, max_dist, trials, similarity, seed, want_trials, api="ransac_correspondences")
+
+
+def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials=100000, similarity=0.9, seed=0, refine=None,
+                      refine_method="point_to_point", src_normals=None, tgt_normals=None):
+    """Register two clouds of any two sizes with neither a network nor a starting pose: src [B,3,Ns], tgt [B,3,Nt] (float32
+    device tensors).  compute_fpfh_feature(k, radius) on both, match_features(mutual), ransac_correspondences(max_dist,
+    trials, similarity, seed), then score_registration at max_dist on the FULL clouds (Open3D's closing evaluation).
+    refine: a correspondence cap; refine_registration(method=refine_method, max_dist=refine) then runs from the RANSAC's pose.
+    src_normals, tgt_normals [B,3,N]: the clouds' normals for the features; None estimates them (estimate_normals, from the
+    features' own search).  An estimated normal's SIGN is arbitrary, and the feature of a point changes with it: two copies of
+    one surface match far better with normals oriented alike (towards the sensor, say) than with estimated ones -- on the
+    test's surface 99.7 % of the one-way matches are the true partner against 18 % at 600 points.
+    Returns a dict: fitness, inlier_rmse, inliers (the score of the RANSAC's pose); R, t, best_trial, pairs and ransac_inliers
+    (the RANSAC's; its `inliers` under that name); corr int32 [B,Ns]; and with refine, `refined`: refine_registration's dict."""
+    from .fpfh import compute_fpfh_feature
+    from .refine import refine_registration
+    from .score import score_registration
+    api = "register_features"
+    if refine is not None and not (math.isfinite(float(refine)) and float(refine) >= 0.0):
+        raise VcrHipError(f"{api}: refine must be None or a finite correspondence cap >= 0, got {refine}")
+    _ransac_checks(api, src, tgt, None, max_dist, trials, similarity, seed, given_corr=False)
+    corr = match_features(compute_fpfh_feature(src, src_normals, k=k, radius=radius),
+                          compute_fpfh_feature(tgt, tgt_normals, k=k, radius=radius), mutual=mutual)
+    r = ransac_correspondences(src, tgt, corr, max_dist, trials, similarity, seed)
+    res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist))
+    res.update(R=r["R"], t=r["t"], best_trial=r["best_trial"], pairs=r["pairs"], ransac_inliers=r["inliers"], corr=corr)
+    if refine is not None:
+        res["refined"] = refine_registration(src, tgt, r["R"], r["t"], float(refine), method=refine_method)
+    return res
