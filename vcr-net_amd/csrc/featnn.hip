@@ -18,18 +18,20 @@
 //   featnn_mutual_kernel    one lane per column of a: nn_idx[i] = j stays iff rev[j] == i.
 // The reverse direction (rev_idx, mutual) is the same three launches with the roles exchanged.  The merge's geometry depends on
 // the column count alone, so every form of the scan returns the same bits.  No atomics.
-#include "common.h"
+#include "seg_scan.h"
 #include "../../include/vcr_hip_match.h"
 
 namespace {
 
 constexpr int FN_BLOCK = 256;
+static_assert(FN_BLOCK == WG_BLOCK, "seg_scan.h serves workgroups of this size");
 constexpr int FN_C = VCR_FEAT_NN_C;
 constexpr int FN_ROW = 36;                                 // floats per transposed row: 144 B, 16-B aligned
 constexpr int FN_MAX_N = 131072;
 constexpr int FN_MAX_SPLITS = 128;
 constexpr int FN_MIN_SEGMENT = 64;                         // the plan cuts no segment shorter than this (a forced split may)
 constexpr int FN_FILL_PER_CU = 16;                         // workgroups per CU the plan cuts the work into, where it can
+constexpr SegLimits FN_LIMITS{FN_MIN_SEGMENT, FN_FILL_PER_CU, FN_MAX_SPLITS};
 
 struct FnRows { const float* x; float* rows; int N; long total; };      // total = B N
 
@@ -58,10 +60,8 @@ struct FnScan {
 template <int Q>
 __global__ __launch_bounds__(FN_BLOCK) void featnn_scan_kernel(FnScan p) {
   const int t = threadIdx.x;
-  const unsigned bid = blockIdx.x;
-  const int s = (int)(bid % (unsigned)p.S);
-  const unsigned rest = bid / (unsigned)p.S;
-  const int blk = (int)(rest % (unsigned)p.nblk), b = (int)(rest / (unsigned)p.nblk);
+  int s, blk, b;
+  seg_workgroup(blockIdx.x, p.S, p.nblk, &s, &blk, &b);
   const int Nq = p.Nq, Nc = p.Nc;
   const float* __restrict__ qx = p.q + (size_t)b * FN_C * Nq;
 
@@ -77,9 +77,8 @@ __global__ __launch_bounds__(FN_BLOCK) void featnn_scan_kernel(FnScan p) {
     bi[q] = -1;
   }
 
-  const long seg_lo = (long)s * p.seg_len;
-  const int lo = seg_lo < Nc ? (int)seg_lo : Nc;
-  const int hi = Nc - lo < p.seg_len ? Nc : lo + p.seg_len;            // [lo, hi) is inside [0, Nc]; empty past the cloud's end
+  int lo, hi;
+  seg_range(s, p.seg_len, Nc, &lo, &hi);
   const float* __restrict__ rows = p.rows + (size_t)b * Nc * FN_ROW;   // (workgroup-uniform, like j below: scalar loads)
 
   auto candidate = [&](int j) {
@@ -115,16 +114,10 @@ struct FnMerge { const float* part_d2; const int* part_idx; int B, N, S; long to
 __global__ __launch_bounds__(FN_BLOCK) void featnn_merge_kernel(FnMerge p) {
   const long g = (long)blockIdx.x * FN_BLOCK + threadIdx.x;
   if (g >= p.total) return;
-  float best = __builtin_huge_valf();
-  int bi = -1;
-  for (int s = 0; s < p.S; ++s) {                          // ascending segments = ascending index
-    const size_t at = (size_t)s * p.total + g;
-    const float d2 = p.part_d2[at];
-    const int i = p.part_idx[at];
-    const bool take = d2 < best;
-    best = take ? d2 : best;
-    bi = take ? i : bi;
-  }
+  float best;
+  int bi;
+  // the candidates [S][B][N] as ONE cloud of B N columns: (s B + b) N + n = s (B N) + g, and B N < 2^31
+  nn_fold(p.part_d2, p.part_idx, 1, (int)p.total, p.S, 0, (int)g, &best, &bi);
   p.idx[g] = bi;
   if (p.d2) p.d2[g] = best;
 }
@@ -141,8 +134,8 @@ __global__ __launch_bounds__(FN_BLOCK) void featnn_mutual_kernel(FnMutual p) {
 }
 
 // How one call runs: fn_plan() validates the arguments and decides the form from them and the CU count, and it is the only
-// place that does.  A direction is (Q, S, seg_len, nblk); the reverse one exists when rev_idx or mutual asks for it.
-struct FnDir { int Q, S, seg_len, nblk; unsigned grid; };
+// place that does.  A direction is Q and the scan's split; the reverse one exists when rev_idx or mutual asks for it.
+struct FnDir { int Q; SegSplit scan; };
 struct FnPlan {
   vcr_feat_nn_args a;
   bool reverse;
@@ -150,57 +143,38 @@ struct FnPlan {
   size_t rows_b, rows_a, part_d2, part_idx, rev_buf, bytes;    // workspace offsets: b's rows | a's rows | candidates | rev
 };
 
-inline size_t fn_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 int fn_dir(int B, int Nq, int Nc, int fq, int fs, int cu, FnDir* d) {
-  auto groups = [&](int q) { return (long)B * ((Nq + FN_BLOCK * q - 1) / (FN_BLOCK * q)); };
-  const long fill = (long)FN_FILL_PER_CU * cu;
-  const long whole = Nc / FN_MIN_SEGMENT;                  // (rounded down: a segment, ceil(Nc / S) rows, is never shorter)
-  const long most = whole < 1 ? 1 : whole < FN_MAX_SPLITS ? whole : FN_MAX_SPLITS;
   // Measured (profiles/match_bench.txt, every Q forced at three shapes): more columns per lane amortise the scalar loads of a
   // candidate row and pack two chains into one v_pk_fma_f32 -- four beat one by 10 % at 16 x 16 384 and 1 x 131 072 rows, at
   // three waves per SIMD -- but only while the searched side can still be cut into `fill` workgroups; at 16 x 1 024 rows,
   // where it cannot, one column per lane (four times the workgroups) is 19-26 % faster.  So the plan takes the most columns per
   // lane that leave `fill` workgroups within reach, then cuts the searched side until they exist, into segments of at least
-  // FN_MIN_SEGMENT rows.
-  int Q = fq;
-  if (!Q) Q = groups(4) * most >= fill ? 4 : groups(2) * most >= fill ? 2 : 1;
-  int S = fs;
-  if (!S) {
-    S = 1;
-    if (groups(Q) < fill) {
-      const long want = (fill + groups(Q) - 1) / groups(Q);
-      S = (int)(want < most ? want : most);
-    }
-  }
-  const long grid = groups(Q) * S;
-  if (grid >= (1L << 31)) return VCR_EUNSUPPORTED;
-  *d = FnDir{Q, S, (Nc + S - 1) / S, (Nq + FN_BLOCK * Q - 1) / (FN_BLOCK * Q), (unsigned)grid};
-  return VCR_OK;
+  // FN_MIN_SEGMENT rows (seg_split, under FN_LIMITS).
+  d->Q = fq ? fq : seg_fills(B, Nq, Nc, 4, cu, FN_LIMITS) ? 4 : seg_fills(B, Nq, Nc, 2, cu, FN_LIMITS) ? 2 : 1;
+  return seg_split(B, Nq, Nc, d->Q, fs, cu, FN_LIMITS, &d->scan);
 }
 
 int fn_plan(const vcr_feat_nn_args& a, int cu, FnPlan* p) {
   *p = FnPlan{a};
   if (!a.a || !a.b || !a.nn_idx || a.B < 1 || a.Ns < 1 || a.Nt < 1) return VCR_EINVAL;
-  const int fq = a.variant & 0xF, fs = (a.variant >> 8) & 0xFF;
-  if ((a.variant & ~0xFF0F) || (fq != 0 && fq != 1 && fq != 2 && fq != 4) || fs > FN_MAX_SPLITS) return VCR_EINVAL;
+  int fq, fs;
+  if (seg_variant(a.variant, SEG_Q_124, FN_LIMITS, &fq, &fs)) return VCR_EINVAL;
   if (a.C != FN_C) return VCR_EUNSUPPORTED;
   const int Nmax = a.Ns > a.Nt ? a.Ns : a.Nt;
   if (a.Ns > FN_MAX_N || a.Nt > FN_MAX_N || (long)a.B * Nmax >= (1L << 31)) return VCR_EUNSUPPORTED;
-  if (cu < 1) cu = 1;
   p->reverse = a.mutual != 0 || a.rev_idx != nullptr;
   int e = fn_dir(a.B, a.Ns, a.Nt, fq, fs, cu, &p->fwd);
   if (e) return e;
   p->rev = FnDir{};
   if (p->reverse && (e = fn_dir(a.B, a.Nt, a.Ns, fq, fs, cu, &p->rev))) return e;
-  size_t cand = (size_t)p->fwd.S * a.B * a.Ns;
-  if (p->reverse && (size_t)p->rev.S * a.B * a.Nt > cand) cand = (size_t)p->rev.S * a.B * a.Nt;
+  size_t cand = (size_t)p->fwd.scan.S * a.B * a.Ns;
+  if (p->reverse && (size_t)p->rev.scan.S * a.B * a.Nt > cand) cand = (size_t)p->rev.scan.S * a.B * a.Nt;
   p->rows_b = 0;
-  p->rows_a = fn_up((size_t)a.B * a.Nt * FN_ROW * 4);
-  p->part_d2 = p->rows_a + (p->reverse ? fn_up((size_t)a.B * a.Ns * FN_ROW * 4) : 0);
-  p->part_idx = p->part_d2 + fn_up(cand * 4);
-  p->rev_buf = p->part_idx + fn_up(cand * 4);
-  p->bytes = p->rev_buf + (p->reverse && !a.rev_idx ? fn_up((size_t)a.B * a.Nt * 4) : 0);
+  p->rows_a = ws_up((size_t)a.B * a.Nt * FN_ROW * 4);
+  p->part_d2 = p->rows_a + (p->reverse ? ws_up((size_t)a.B * a.Ns * FN_ROW * 4) : 0);
+  p->part_idx = p->part_d2 + ws_up(cand * 4);
+  p->rev_buf = p->part_idx + ws_up(cand * 4);
+  p->bytes = p->rev_buf + (p->reverse && !a.rev_idx ? ws_up((size_t)a.B * a.Nt * 4) : 0);
   return VCR_OK;
 }
 
@@ -213,14 +187,14 @@ int fn_search(const FnDir& d, const float* q, const float* c, int B, int Nq, int
   const FnRows r{c, rows, Nc, (long)B * Nc};
   hipLaunchKernelGGL(featnn_rows_kernel, dim3(fn_grid(r.total)), dim3(FN_BLOCK), 0, s, r);
   if ((e = VCR_LAUNCH_RC())) return e;
-  const FnScan sc{q, rows, B, Nq, Nc, d.S, d.seg_len, d.nblk, part_d2, part_idx};
+  const FnScan sc{q, rows, B, Nq, Nc, d.scan.S, d.scan.seg_len, d.scan.nblk, part_d2, part_idx};
   switch (d.Q) {
-    case 4: hipLaunchKernelGGL(featnn_scan_kernel<4>, dim3(d.grid), dim3(FN_BLOCK), 0, s, sc); break;
-    case 2: hipLaunchKernelGGL(featnn_scan_kernel<2>, dim3(d.grid), dim3(FN_BLOCK), 0, s, sc); break;
-    default: hipLaunchKernelGGL(featnn_scan_kernel<1>, dim3(d.grid), dim3(FN_BLOCK), 0, s, sc); break;
+    case 4: hipLaunchKernelGGL(featnn_scan_kernel<4>, dim3(d.scan.grid), dim3(FN_BLOCK), 0, s, sc); break;
+    case 2: hipLaunchKernelGGL(featnn_scan_kernel<2>, dim3(d.scan.grid), dim3(FN_BLOCK), 0, s, sc); break;
+    default: hipLaunchKernelGGL(featnn_scan_kernel<1>, dim3(d.scan.grid), dim3(FN_BLOCK), 0, s, sc); break;
   }
   if ((e = VCR_LAUNCH_RC())) return e;
-  const FnMerge mg{part_d2, part_idx, B, Nq, d.S, (long)B * Nq, idx, d2};
+  const FnMerge mg{part_d2, part_idx, B, Nq, d.scan.S, (long)B * Nq, idx, d2};
   hipLaunchKernelGGL(featnn_merge_kernel, dim3(fn_grid(mg.total)), dim3(FN_BLOCK), 0, s, mg);
   return VCR_LAUNCH_RC();
 }
@@ -238,7 +212,7 @@ extern "C" int vcr_feat_nn_form(const vcr_feat_nn_args* ua, int cu_count, int* q
   const int e = fn_plan(a, cu_count ? cu_count : vcr_cu_count(), &p);
   if (e) return e;
   if (queries_per_lane) *queries_per_lane = p.fwd.Q;
-  if (target_splits) *target_splits = p.fwd.S;
+  if (target_splits) *target_splits = p.fwd.scan.S;
   return VCR_OK;
 }
 

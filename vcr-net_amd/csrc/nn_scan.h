@@ -1,17 +1,19 @@
 // The one brute-force nearest-neighbour scan of the full clouds and the plan that fixes its form, shared by
 // nnscore.hip (vcr_nn_score_f32) and refine.hip (vcr_refine_f32, which runs it once per round behind a per-cloud gate).
 #pragma once
-#include "common.h"
+#include "seg_scan.h"
 #include "../../include/vcr_hip_score.h"
 
 namespace {
 
 constexpr int NN_BLOCK = 256;
+static_assert(NN_BLOCK == WG_BLOCK, "seg_scan.h and wg_scan.h serve workgroups of this size");
 constexpr int NN_TILE = 1024;                              // target points per LDS tile: 3 planes x 4 KB
 constexpr int NN_MAX_N = 131072;                           // the kNN / FPS entry points' limit (vcr_hip.h)
 constexpr int NN_MAX_SPLITS = 128;
 constexpr int NN_MIN_SEGMENT = 256;                        // the plan cuts no segment shorter than this (a forced split may)
 constexpr int NN_FILL_PER_CU = 64;                         // workgroups per CU the plan cuts the work into, where it can
+constexpr SegLimits NN_LIMITS{NN_MIN_SEGMENT, NN_FILL_PER_CU, NN_MAX_SPLITS};
 
 struct NnPartial { double sum; int count; int pad; };      // one per 256 source points
 static_assert(sizeof(NnPartial) == 16, "workspace layout");
@@ -27,10 +29,8 @@ template <int Q>
 __global__ __launch_bounds__(NN_BLOCK) void nn_scan_kernel(NnScan p) {
   __shared__ __attribute__((aligned(16))) float lx[NN_TILE], ly[NN_TILE], lz[NN_TILE];
   const int t = threadIdx.x;
-  const unsigned bid = blockIdx.x;
-  const int s = (int)(bid % (unsigned)p.S);
-  const unsigned rest = bid / (unsigned)p.S;
-  const int blk = (int)(rest % (unsigned)p.nblk), b = (int)(rest / (unsigned)p.nblk);
+  int s, blk, b;
+  seg_workgroup(blockIdx.x, p.S, p.nblk, &s, &blk, &b);
   if (p.live && !p.live[b]) return;                        // (workgroup-uniform, before the first barrier)
   const int Ns = p.Ns, Nt = p.Nt;
   const float* __restrict__ sx = p.src + (size_t)b * 3 * Ns;
@@ -59,9 +59,8 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_scan_kernel(NnScan p) {
     bi[q] = -1;
   }
 
-  const long seg_lo = (long)s * p.seg_len;
-  const int lo = seg_lo < Nt ? (int)seg_lo : Nt;
-  const int hi = Nt - lo < p.seg_len ? Nt : lo + p.seg_len;           // [lo, hi) is inside [0, Nt]; empty past the cloud's end
+  int lo, hi;
+  seg_range(s, p.seg_len, Nt, &lo, &hi);
   const float nan = __uint_as_float(0x7FC00000u);
   for (int t0 = lo; t0 < hi; t0 += NN_TILE) {                         // (workgroup-uniform: the barriers are met by all)
     const int cnt = hi - t0 < NN_TILE ? hi - t0 : NN_TILE;
@@ -98,34 +97,16 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_scan_kernel(NnScan p) {
   }
 }
 
-// One source point's neighbour from its S candidates, ascending segments = ascending target index: the strict < keeps the
-// lowest index among equals, as inside a segment.
-__device__ __forceinline__ void nn_fold(const float* part_d2, const int* part_idx, int B, int Ns, int S, int b, int n,
-                                        float* best_out, int* bi_out) {
-  float best = __builtin_huge_valf();
-  int bi = -1;
-  for (int s = 0; s < S; ++s) {
-    const size_t at = ((size_t)s * B + b) * (size_t)Ns + n;
-    const float d2 = part_d2[at];
-    const int i = part_idx[at];
-    const bool take = d2 < best;
-    best = take ? d2 : best;
-    bi = take ? i : bi;
-  }
-  *best_out = best; *bi_out = bi;
-}
-
 // How one call runs.  nn_plan() validates the arguments and decides the form from them and the CU count, and it is the only
 // place that does: the entry point launches what the plan says, vcr_nn_score_form and _workspace_bytes answer from it.
 struct NnPlan {
   vcr_nn_score_args a;
-  int Q, S, seg_len;
-  unsigned scan_grid, merge_grid;
-  int nblk_scan, nblk;                                     // workgroups per cloud: of the scan (and segment), of the merge
+  int Q;
+  SegSplit scan;
+  unsigned merge_grid;
+  int nblk;                                                // workgroups per cloud of the merge
   size_t part_bytes, partial_off, bytes;                   // workspace: part_d2 | part_idx | partials
 };
-
-inline size_t nn_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -134,40 +115,21 @@ static int nn_plan(const vcr_nn_score_args& a, int cu, NnPlan* p) {
   if (!a.src || !a.tgt || !a.fitness || !a.rmse || a.B < 1 || a.Ns < 1 || a.Nt < 1) return VCR_EINVAL;
   if ((a.R == nullptr) != (a.t == nullptr)) return VCR_EINVAL;
   if (!(a.max_dist >= 0.f) || a.max_dist == __builtin_huge_valf()) return VCR_EINVAL;      // negative, NaN, +inf
-  const int fq = a.variant & 0xF, fs = (a.variant >> 8) & 0xFF;
-  if ((a.variant & ~0xFF0F) || (fq != 0 && fq != 1 && fq != 2 && fq != 4) || fs > NN_MAX_SPLITS) return VCR_EINVAL;
+  int fq, fs;
+  if (seg_variant(a.variant, SEG_Q_124, NN_LIMITS, &fq, &fs)) return VCR_EINVAL;
   if (a.Ns > NN_MAX_N || a.Nt > NN_MAX_N || (long)a.B * (a.Ns > a.Nt ? a.Ns : a.Nt) >= (1L << 31)) return VCR_EUNSUPPORTED;
-  if (cu < 1) cu = 1;
-  auto groups = [&](int q) { return (long)a.B * ((a.Ns + NN_BLOCK * q - 1) / (NN_BLOCK * q)); };
   // Measured (profiles/nnscore_bench.txt, every Q x S forced at four shapes): one point per lane wins at every shape -- at an
   // equal number of workgroups two per lane lose 10-15 % (65 VGPRs, seven waves per SIMD) and four 4-8 % -- and the scan keeps
   // gaining until a CU has been dealt about 64 workgroups, eight rounds of the eight (32 waves) it holds.  So the plan takes
-  // Q = 1 and cuts the target; Q = 2 / 4 stay as forced forms.
-  const long fill = (long)NN_FILL_PER_CU * cu;
-  const long whole = a.Nt / NN_MIN_SEGMENT;                // (rounded down: a segment, ceil(Nt / S) points, is never shorter)
-  const long most = whole < 1 ? 1 : whole < NN_MAX_SPLITS ? whole : NN_MAX_SPLITS;
-  const int Q = fq ? fq : 1;
-  // S: 1 whenever the source alone fills the CUs; else the target is cut until `fill` workgroups exist, into segments of at
-  // least NN_MIN_SEGMENT points
-  int S = fs;
-  if (!S) {
-    S = 1;
-    if (groups(Q) < fill) {
-      const long want = (fill + groups(Q) - 1) / groups(Q);
-      S = (int)(want < most ? want : most);
-    }
-  }
-  p->Q = Q; p->S = S;
-  p->seg_len = (a.Nt + S - 1) / S;
-  p->nblk_scan = (a.Ns + NN_BLOCK * Q - 1) / (NN_BLOCK * Q);
+  // Q = 1 and cuts the target (seg_split, under NN_LIMITS); Q = 2 / 4 stay as forced forms.
+  p->Q = fq ? fq : 1;
+  const int e = seg_split(a.B, a.Ns, a.Nt, p->Q, fs, cu, NN_LIMITS, &p->scan);
+  if (e) return e;
   p->nblk = (a.Ns + NN_BLOCK - 1) / NN_BLOCK;
-  const long scan = groups(Q) * S;
-  if (scan >= (1L << 31)) return VCR_EUNSUPPORTED;
-  p->scan_grid = (unsigned)scan;
   p->merge_grid = (unsigned)((long)a.B * p->nblk);
-  p->part_bytes = nn_up((size_t)S * a.B * a.Ns * 4);
+  p->part_bytes = ws_up((size_t)p->scan.S * a.B * a.Ns * 4);
   p->partial_off = 2 * p->part_bytes;
-  p->bytes = p->partial_off + nn_up((size_t)a.B * p->nblk * sizeof(NnPartial));
+  p->bytes = p->partial_off + ws_up((size_t)a.B * p->nblk * sizeof(NnPartial));
   return VCR_OK;
 }
 
@@ -175,12 +137,12 @@ static int nn_plan(const vcr_nn_score_args& a, int cu, NnPlan* p) {
 static int nn_scan_launch(const NnPlan& p, void* workspace, const int* live, hipStream_t s) {
   unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
   const vcr_nn_score_args& a = p.a;
-  const NnScan sc{a.src, a.tgt, a.R, a.t, a.B, a.Ns, a.Nt, p.S, p.seg_len, p.nblk_scan,
+  const NnScan sc{a.src, a.tgt, a.R, a.t, a.B, a.Ns, a.Nt, p.scan.S, p.scan.seg_len, p.scan.nblk,
                   reinterpret_cast<float*>(w), reinterpret_cast<int*>(w + p.part_bytes), live};
   switch (p.Q) {
-    case 4: hipLaunchKernelGGL(nn_scan_kernel<4>, dim3(p.scan_grid), dim3(NN_BLOCK), 0, s, sc); break;
-    case 2: hipLaunchKernelGGL(nn_scan_kernel<2>, dim3(p.scan_grid), dim3(NN_BLOCK), 0, s, sc); break;
-    default: hipLaunchKernelGGL(nn_scan_kernel<1>, dim3(p.scan_grid), dim3(NN_BLOCK), 0, s, sc); break;
+    case 4: hipLaunchKernelGGL(nn_scan_kernel<4>, dim3(p.scan.grid), dim3(NN_BLOCK), 0, s, sc); break;
+    case 2: hipLaunchKernelGGL(nn_scan_kernel<2>, dim3(p.scan.grid), dim3(NN_BLOCK), 0, s, sc); break;
+    default: hipLaunchKernelGGL(nn_scan_kernel<1>, dim3(p.scan.grid), dim3(NN_BLOCK), 0, s, sc); break;
   }
   return VCR_LAUNCH_RC();
 }

@@ -17,7 +17,8 @@
 //                       (segments ascend in target index: the lowest-index rule survives the split), writes nn_idx / nn_d2,
 //                       and reduces its 256 points to one (fp64 sum, count) partial in a fixed order.
 //   nn_final_kernel     one workgroup per cloud: the partials in ascending order, then inliers / sum_d2 / fitness / rmse.
-// The geometry of the last two depends on Ns alone, so every form of the first returns the same bits.  No atomics.
+// The geometry of the last two depends on Ns alone, so every form of the first returns the same bits.  No atomics.  The scan's
+// frame (seg_scan.h) and the two reductions (wg_scan.h) are the ones every scan of the library uses.
 #include "nn_scan.h"
 
 namespace {
@@ -44,18 +45,10 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_merge_kernel(NnMerge p) {
     if (p.nn_d2) p.nn_d2[o] = best;
   }
   const bool in = n < p.Ns && bi >= 0 && best <= p.max_d2;
-  double v = in ? (double)best : 0.;
-  int c = in ? 1 : 0;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) { v += __shfl_xor(v, o, 64); c += __shfl_xor(c, o, 64); }
-  if ((t & 63) == 0) { wsum[t >> 6] = v; wcnt[t >> 6] = c; }
-  __syncthreads();
-  if (t == 0) {
-    double sum = wsum[0];
-    int cnt = wcnt[0];
-    for (int w = 1; w < NN_BLOCK / 64; ++w) { sum += wsum[w]; cnt += wcnt[w]; }
-    p.partial[(size_t)b * p.nblk + blk] = NnPartial{sum, cnt, 0};
-  }
+  double sum = 0.;
+  int cnt = 0;
+  wg_sum_count(in ? (double)best : 0., in ? 1 : 0, t, wsum, wcnt, &sum, &cnt);
+  if (t == 0) p.partial[(size_t)b * p.nblk + blk] = NnPartial{sum, cnt, 0};
 }
 
 struct NnFinal {
@@ -70,14 +63,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_final_kernel(NnFinal p) {
   const NnPartial* part = p.partial + (size_t)b * p.nblk;
   double sum = 0.;
   int cnt = 0;
-  for (int c0 = 0; c0 < p.nblk; c0 += NN_BLOCK) {          // (workgroup-uniform)
-    const int m = p.nblk - c0 < NN_BLOCK ? p.nblk - c0 : NN_BLOCK;
-    __syncthreads();
-    if (t < m) { ls[t] = part[c0 + t].sum; lc[t] = part[c0 + t].count; }
-    __syncthreads();
-    if (t == 0)
-      for (int i = 0; i < m; ++i) { sum += ls[i]; cnt += lc[i]; }     // ascending, one thread: the order is Ns's alone
-  }
+  wg_fold(p.nblk, [&](int i, double* s, int* c) { *s = part[i].sum; *c = part[i].count; }, t, ls, lc, &sum, &cnt);
   if (t == 0) {
     if (p.inliers) p.inliers[b] = cnt;
     if (p.sum_d2) p.sum_d2[b] = sum;
@@ -99,7 +85,7 @@ extern "C" int vcr_nn_score_form(const vcr_nn_score_args* ua, int cu_count, int*
   const int e = nn_plan(a, cu_count ? cu_count : vcr_cu_count(), &p);
   if (e) return e;
   if (queries_per_lane) *queries_per_lane = p.Q;
-  if (target_splits) *target_splits = p.S;
+  if (target_splits) *target_splits = p.scan.S;
   return VCR_OK;
 }
 
@@ -128,7 +114,7 @@ extern "C" int vcr_nn_score_f32(const vcr_nn_score_args* ua, void* workspace, si
   int* part_idx = reinterpret_cast<int*>(w + p.part_bytes);
   NnPartial* partial = reinterpret_cast<NnPartial*>(w + p.partial_off);
   if ((e = nn_scan_launch(p, workspace, nullptr, s))) return e;
-  const NnMerge mg{part_d2, part_idx, a.B, a.Ns, p.S, p.nblk, a.max_dist * a.max_dist, a.nn_idx, a.nn_d2, partial};
+  const NnMerge mg{part_d2, part_idx, a.B, a.Ns, p.scan.S, p.nblk, a.max_dist * a.max_dist, a.nn_idx, a.nn_d2, partial};
   hipLaunchKernelGGL(nn_merge_kernel, dim3(p.merge_grid), dim3(NN_BLOCK), 0, s, mg);
   if ((e = VCR_LAUNCH_RC())) return e;
   const NnFinal fin{partial, a.Ns, p.nblk, a.inliers, a.sum_d2, a.fitness, a.rmse};

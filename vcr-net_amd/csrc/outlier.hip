@@ -12,7 +12,7 @@
 //   outlier_offsets_kernel  one workgroup per cloud: the exclusive scan of those counts, count[b]
 //   outlier_write_kernel    one lane per point writes ONE slot of points / index: a kept point its own (the block's offset + its
 //                           rank among the block's kept), a dropped one the padding of slot count + (its rank among the dropped)
-// vcr_outlier_radius_f32, four launches (the plan is nn_plan's for (B, N, N); vcr_outlier_radius_args.variant forces S):
+// vcr_outlier_radius_f32, four launches (the scan is cut as nn_plan cuts (B, N, N); vcr_outlier_radius_args.variant forces S):
 //   outlier_count_kernel    nn_scan_kernel<1>'s structure (nn_scan.h) on the cloud against itself: tiles of NN_TILE points
 //                           through three LDS planes, a NaN tail, broadcast ds_read_b128; per pair the distance, one compare and
 //                           one add; a count per (segment, point)
@@ -25,44 +25,12 @@
 
 namespace {
 
-typedef unsigned long long u64;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct OlStat { double mu, var, sigma, thr; int n; int pad; };        // one per cloud
 static_assert(sizeof(OlStat) == 40, "workspace layout");
 
 __device__ __forceinline__ bool ol_finite(float v) { return fabsf(v) < __builtin_huge_valf(); }
-
-// The workgroup's 256 values in sum_d2's order (nn_merge_kernel): the wave butterfly 32 ... 1, then the four waves ascending.
-// Thread 0 returns the sums; wsum / wcnt are free again after the next barrier.
-__device__ __forceinline__ void ol_block_sum(double v, int c, int t, double* wsum, int* wcnt, double* sum, int* cnt) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) { v += __shfl_xor(v, o, 64); c += __shfl_xor(c, o, 64); }
-  if ((t & 63) == 0) { wsum[t >> 6] = v; wcnt[t >> 6] = c; }
-  __syncthreads();
-  if (t == 0) {
-    double s = wsum[0];
-    int n = wcnt[0];
-    for (int w = 1; w < NN_BLOCK / 64; ++w) { s += wsum[w]; n += wcnt[w]; }
-    *sum = s; *cnt = n;
-  }
-}
-
-// One cloud's partials in ascending order, by thread 0 (nn_final_kernel's loop: the order is N's alone)
-__device__ __forceinline__ void ol_fold(const double* psum, const int* pcnt, int nblk, int t, double* ls, int* lc,
-                                        double* sum, int* cnt) {
-  double s = 0.;
-  int n = 0;
-  for (int c0 = 0; c0 < nblk; c0 += NN_BLOCK) {            // (workgroup-uniform)
-    const int m = nblk - c0 < NN_BLOCK ? nblk - c0 : NN_BLOCK;
-    __syncthreads();
-    if (t < m) { ls[t] = psum[c0 + t]; lc[t] = pcnt ? pcnt[c0 + t] : 0; }
-    __syncthreads();
-    if (t == 0)
-      for (int i = 0; i < m; ++i) { s += ls[i]; n += lc[i]; }
-  }
-  *sum = s; *cnt = n;
-}
 
 struct OlDist {
   const float* xyz4; const int* idx; int N, k, nblk;
@@ -99,7 +67,7 @@ __global__ __launch_bounds__(NN_BLOCK) void outlier_dist_kernel(OlDist p) {
   }
   double sum = 0.;
   int cnt = 0;
-  ol_block_sum(v, c, t, wsum, wcnt, &sum, &cnt);
+  wg_sum_count(v, c, t, wsum, wcnt, &sum, &cnt);
   if (t == 0) { p.psum[(size_t)b * p.nblk + blk] = sum; p.pcnt[(size_t)b * p.nblk + blk] = cnt; }
 }
 
@@ -109,7 +77,8 @@ __global__ __launch_bounds__(NN_BLOCK) void outlier_mu_kernel(const double* psum
   const int t = threadIdx.x, b = blockIdx.x;
   double sum = 0.;
   int n = 0;
-  ol_fold(psum + (size_t)b * nblk, pcnt + (size_t)b * nblk, nblk, t, ls, lc, &sum, &n);
+  psum += (size_t)b * nblk; pcnt += (size_t)b * nblk;
+  wg_fold(nblk, [&](int i, double* s, int* c) { *s = psum[i]; *c = pcnt[i]; }, t, ls, lc, &sum, &n);
   if (t == 0) {
     st[b].n = n;
     st[b].mu = sum / (double)n;                            // (n = 0: 0 / 0, the NaN the header promises)
@@ -134,7 +103,7 @@ __global__ __launch_bounds__(NN_BLOCK) void outlier_dev_kernel(OlDev p) {
   }
   double sum = 0.;
   int cnt = 0;
-  ol_block_sum(v, 0, t, wsum, wcnt, &sum, &cnt);
+  wg_sum_count(v, 0, t, wsum, wcnt, &sum, &cnt);
   if (t == 0) p.pdev[(size_t)b * p.nblk + blk] = sum;
 }
 
@@ -145,7 +114,8 @@ __global__ __launch_bounds__(NN_BLOCK) void outlier_sigma_kernel(const double* p
   const int t = threadIdx.x, b = blockIdx.x;
   double sum = 0.;
   int unused = 0;
-  ol_fold(pdev + (size_t)b * nblk, nullptr, nblk, t, ls, lc, &sum, &unused);
+  pdev += (size_t)b * nblk;
+  wg_fold(nblk, [&](int i, double* s, int* c) { *s = pdev[i]; *c = 0; }, t, ls, lc, &sum, &unused);
   if (t == 0) {
     const int n = st[b].n;
     const double mu = st[b].mu;
@@ -175,18 +145,6 @@ __device__ __forceinline__ bool ol_keep(const OlTail& p, int b, size_t o) {
   return ol_finite(m) && (double)m <= p.st[b].thr;         // (a NaN threshold keeps nothing)
 }
 
-// The number of lanes of the workgroup whose flag is set, and this lane's rank among them (lanes ascending): voxel.hip's vx_rank
-__device__ __forceinline__ int ol_rank(bool flag, int t, int* wcnt, int* total) {
-  const u64 bal = __ballot(flag);
-  const int lane = t & 63, w = t >> 6;
-  if (lane == 0) wcnt[w] = __popcll(bal);
-  __syncthreads();
-  int below = 0, all = 0;
-  for (int k = 0; k < NN_BLOCK / 64; ++k) { below += k < w ? wcnt[k] : 0; all += wcnt[k]; }
-  *total = all;
-  return below + __popcll(bal & ((1ull << lane) - 1ull));
-}
-
 __global__ __launch_bounds__(NN_BLOCK) void outlier_mark_kernel(OlTail p) {
   __shared__ int wcnt[NN_BLOCK / 64];
   const int t = threadIdx.x;
@@ -194,36 +152,15 @@ __global__ __launch_bounds__(NN_BLOCK) void outlier_mark_kernel(OlTail p) {
   const int i = blk * NN_BLOCK + t;
   const bool keep = i < p.N && ol_keep(p, b, (size_t)b * p.N + (i < p.N ? i : 0));
   int kept;
-  ol_rank(keep, t, wcnt, &kept);
+  wg_rank(keep, t, wcnt, &kept);
   if (t == 0) p.blkcnt[(size_t)b * p.nblk + blk] = kept;
 }
 
-// voxel_offsets_kernel's scan (voxel.hip): two counts a lane, a wave scan, four wave totals
 __global__ __launch_bounds__(NN_BLOCK) void outlier_offsets_kernel(int* blkcnt, int nblk, int* count) {
   __shared__ int wtot[NN_BLOCK / 64];
-  const int t = threadIdx.x, b = blockIdx.x, lane = t & 63, w = t >> 6;
-  int* cnt = blkcnt + (size_t)b * nblk;                    // in place: a lane reads and writes its own two entries
-  int carry = 0;
-  for (int c0 = 0; c0 < nblk; c0 += 2 * NN_BLOCK) {        // (workgroup-uniform; one round up to 131 072 points)
-    const int i0 = c0 + 2 * t, i1 = i0 + 1;
-    const int a0 = i0 < nblk ? cnt[i0] : 0, a1 = i1 < nblk ? cnt[i1] : 0;
-    int incl = a0 + a1;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(incl, o, 64);
-      incl += lane >= o ? v : 0;
-    }
-    __syncthreads();                                       // the previous round's totals have been read
-    if (lane == 63) wtot[w] = incl;
-    __syncthreads();
-    int below = 0, all = 0;
-    for (int k = 0; k < NN_BLOCK / 64; ++k) { below += k < w ? wtot[k] : 0; all += wtot[k]; }
-    const int excl = carry + below + incl - (a0 + a1);
-    if (i0 < nblk) cnt[i0] = excl;
-    if (i1 < nblk) cnt[i1] = excl + a0;
-    carry += all;
-  }
-  if (t == 0) count[b] = carry;
+  const int b = blockIdx.x;
+  const int kept = wg_offsets(blkcnt + (size_t)b * nblk, nblk, wtot);
+  if (threadIdx.x == 0) count[b] = kept;
 }
 
 __global__ __launch_bounds__(NN_BLOCK) void outlier_write_kernel(OlTail p) {
@@ -234,7 +171,7 @@ __global__ __launch_bounds__(NN_BLOCK) void outlier_write_kernel(OlTail p) {
   const size_t row = (size_t)b * N;
   const bool keep = i < N && ol_keep(p, b, row + (i < N ? i : 0));
   int kept;
-  const int rank = ol_rank(keep, t, wcnt, &kept);
+  const int rank = wg_rank(keep, t, wcnt, &kept);
   if (i >= N) return;
   const int before = p.blkcnt[(size_t)b * p.nblk + blk] + rank;       // kept points below i: <= i
   // a kept point's slot is its rank among the kept, < count; a dropped one's count + its rank among the dropped, i - before:
@@ -266,10 +203,8 @@ struct OlCount {
 __global__ __launch_bounds__(NN_BLOCK) void outlier_count_kernel(OlCount p) {
   __shared__ __attribute__((aligned(16))) float lx[NN_TILE], ly[NN_TILE], lz[NN_TILE];
   const int t = threadIdx.x;
-  const unsigned bid = blockIdx.x;
-  const int s = (int)(bid % (unsigned)p.S);
-  const unsigned rest = bid / (unsigned)p.S;
-  const int blk = (int)(rest % (unsigned)p.nblk), b = (int)(rest / (unsigned)p.nblk);
+  int s, blk, b;
+  seg_workgroup(blockIdx.x, p.S, p.nblk, &s, &blk, &b);
   const int N = p.N;
   const float* __restrict__ x = p.xyz + (size_t)b * 3 * N;
   const int i = blk * NN_BLOCK + t;
@@ -279,9 +214,8 @@ __global__ __launch_bounds__(NN_BLOCK) void outlier_count_kernel(OlCount p) {
   const float r2 = p.r2;
   int c0 = 0, c1 = 0;                                      // the even and the odd points of a tile
 
-  const long seg_lo = (long)s * p.seg_len;
-  const int lo = seg_lo < N ? (int)seg_lo : N;
-  const int hi = N - lo < p.seg_len ? N : lo + p.seg_len;              // [lo, hi) is inside [0, N]; empty past the cloud's end
+  int lo, hi;
+  seg_range(s, p.seg_len, N, &lo, &hi);
   for (int t0 = lo; t0 < hi; t0 += NN_TILE) {                          // (workgroup-uniform: the barriers are met by all)
     const int cnt = hi - t0 < NN_TILE ? hi - t0 : NN_TILE;
     const int cnt8 = (cnt + 7) & ~7;                                   // <= NN_TILE; the tail is NaN: its d2 is in no sphere
@@ -331,7 +265,7 @@ __global__ __launch_bounds__(NN_BLOCK) void outlier_merge_kernel(OlMerge p) {
     if (p.neighbours) p.neighbours[o] = c;
   }
   int kept;
-  ol_rank(i < p.N && c > p.nb_points, t, wcnt, &kept);
+  wg_rank(i < p.N && c > p.nb_points, t, wcnt, &kept);
   if (t == 0) p.blkcnt[(size_t)b * p.nblk + blk] = kept;
 }
 
@@ -354,8 +288,8 @@ struct OlStatPlan {
 
 struct OlRadiusPlan {
   vcr_outlier_radius_args a;
-  int S, seg_len, nblk;
-  unsigned scan_grid, point_grid;
+  SegSplit scan;                                           // (one point per lane: its nblk is the per-point launches' too)
+  unsigned point_grid;
   size_t cnt_off, blk_off, bytes;                          // workspace: part | cnt | blkcnt
 };
 
@@ -369,12 +303,12 @@ static int outlier_stat_plan(const vcr_outlier_stat_args& a, OlStatPlan* p) {
   p->nblk = (a.N + NN_BLOCK - 1) / NN_BLOCK;
   p->point_grid = (unsigned)((long)a.B * p->nblk);
   const size_t parts = (size_t)a.B * p->nblk;
-  p->st_off = nn_up((size_t)a.B * a.N * 4);
-  p->psum_off = p->st_off + nn_up((size_t)a.B * sizeof(OlStat));
-  p->pdev_off = p->psum_off + nn_up(parts * 8);
-  p->pcnt_off = p->pdev_off + nn_up(parts * 8);
-  p->blk_off = p->pcnt_off + nn_up(parts * 4);
-  p->bytes = p->blk_off + nn_up(parts * 4);
+  p->st_off = ws_up((size_t)a.B * a.N * 4);
+  p->psum_off = p->st_off + ws_up((size_t)a.B * sizeof(OlStat));
+  p->pdev_off = p->psum_off + ws_up(parts * 8);
+  p->pcnt_off = p->pdev_off + ws_up(parts * 8);
+  p->blk_off = p->pcnt_off + ws_up(parts * 4);
+  p->bytes = p->blk_off + ws_up(parts * 4);
   return VCR_OK;
 }
 
@@ -424,29 +358,21 @@ extern "C" int vcr_outlier_stat_f32(const vcr_outlier_stat_args* ua, void* works
   return ol_compact(tl, a.B, p.point_grid, s);
 }
 
-// The scan's split is nn_plan's for B clouds of N points against themselves, as voxel_plan takes it
+// The scan is cut as nn_plan cuts B clouds of N points against themselves, one point per lane, as voxel_plan does
 static int outlier_radius_plan(const vcr_outlier_radius_args& a, int cu, OlRadiusPlan* p) {
   *p = OlRadiusPlan{a};
   if (!a.xyz || !a.points || !a.count || a.B < 1 || a.nb_points < 0) return VCR_EINVAL;
   if (!(a.radius > 0.f) || a.radius == __builtin_huge_valf()) return VCR_EINVAL;             // <= 0, NaN, +inf
-  const int fq = a.variant & 0xF, fs = (a.variant >> 8) & 0xFF;
-  if ((a.variant & ~0xFF0F) || fq > 1 || fs > NN_MAX_SPLITS) return VCR_EINVAL;
+  int fq, fs;
+  if (seg_variant(a.variant, SEG_Q_1, NN_LIMITS, &fq, &fs)) return VCR_EINVAL;
   if (a.N < 1 || a.N > NN_MAX_N || (long)a.B * a.N >= (1L << 31)) return VCR_EUNSUPPORTED;
-  vcr_nn_score_args n{};
-  n.struct_bytes = (uint32_t)sizeof(n);
-  n.src = n.tgt = a.xyz;
-  n.fitness = n.rmse = a.points;                           // (nn_plan only asks that they are given)
-  n.B = a.B; n.Ns = n.Nt = a.N;
-  n.variant = a.variant;
-  NnPlan np;
-  const int e = nn_plan(n, cu, &np);
+  const int e = seg_split(a.B, a.N, a.N, 1, fs, cu, NN_LIMITS, &p->scan);
   if (e) return e;
-  p->S = np.S; p->seg_len = np.seg_len; p->nblk = np.nblk;
-  p->scan_grid = np.scan_grid; p->point_grid = np.merge_grid;
+  p->point_grid = (unsigned)((long)a.B * p->scan.nblk);
   const size_t BN = (size_t)a.B * a.N;
-  p->cnt_off = nn_up((size_t)np.S * BN * 4);
-  p->blk_off = p->cnt_off + nn_up(BN * 4);
-  p->bytes = p->blk_off + nn_up((size_t)a.B * np.nblk * 4);
+  p->cnt_off = ws_up((size_t)p->scan.S * BN * 4);
+  p->blk_off = p->cnt_off + ws_up(BN * 4);
+  p->bytes = p->blk_off + ws_up((size_t)a.B * p->scan.nblk * 4);
   return VCR_OK;
 }
 
@@ -461,7 +387,7 @@ extern "C" int vcr_outlier_radius_form(const vcr_outlier_radius_args* ua, int cu
   const int e = outlier_radius_plan(a, cu_count ? cu_count : vcr_cu_count(), &p);
   if (e) return e;
   if (points_per_lane) *points_per_lane = 1;
-  if (splits) *splits = p.S;
+  if (splits) *splits = p.scan.S;
   return VCR_OK;
 }
 
@@ -491,12 +417,12 @@ extern "C" int vcr_outlier_radius_f32(const vcr_outlier_radius_args* ua, void* w
   int* cnt = reinterpret_cast<int*>(w + p.cnt_off);
   int* blk = reinterpret_cast<int*>(w + p.blk_off);
 
-  const OlCount sc{a.xyz, a.B, a.N, p.S, p.seg_len, p.nblk, a.radius * a.radius, part};
-  hipLaunchKernelGGL(outlier_count_kernel, dim3(p.scan_grid), dim3(NN_BLOCK), 0, s, sc);
+  const OlCount sc{a.xyz, a.B, a.N, p.scan.S, p.scan.seg_len, p.scan.nblk, a.radius * a.radius, part};
+  hipLaunchKernelGGL(outlier_count_kernel, dim3(p.scan.grid), dim3(NN_BLOCK), 0, s, sc);
   if ((e = VCR_LAUNCH_RC())) return e;
-  const OlMerge mg{part, a.B, a.N, p.S, p.nblk, a.nb_points, cnt, a.neighbours, blk};
+  const OlMerge mg{part, a.B, a.N, p.scan.S, p.scan.nblk, a.nb_points, cnt, a.neighbours, blk};
   hipLaunchKernelGGL(outlier_merge_kernel, dim3(p.point_grid), dim3(NN_BLOCK), 0, s, mg);
   if ((e = VCR_LAUNCH_RC())) return e;
-  const OlTail tl{nullptr, nullptr, cnt, a.nb_points, nullptr, a.xyz, a.N, p.nblk, blk, a.points, a.count, a.index};
+  const OlTail tl{nullptr, nullptr, cnt, a.nb_points, nullptr, a.xyz, a.N, p.scan.nblk, blk, a.points, a.count, a.index};
   return ol_compact(tl, a.B, p.point_grid, s);
 }

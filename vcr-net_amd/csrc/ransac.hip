@@ -14,7 +14,7 @@
 //   ransac_best_kernel    one workgroup per cloud: the maximum of the 64-bit key (count << 32) | (0xFFFFFFFF - t) over the
 //                         valid trials -- the highest count, the lowest trial among equals -- and the outputs.
 // Every result is a function of the cloud alone; all writes are plain vector stores.
-#include "common.h"
+#include "seg_scan.h"
 #include "svd3.h"
 #include "../../include/vcr_hip_match.h"
 
@@ -23,6 +23,7 @@ namespace {
 typedef unsigned long long u64;
 
 constexpr int RS_BLOCK = 256;
+static_assert(RS_BLOCK == WG_BLOCK, "wg_scan.h serves workgroups of this size");
 constexpr int RS_MAX_N = 131072;
 
 struct RsWork {                                            // the workspace, per cloud b
@@ -49,20 +50,16 @@ __global__ __launch_bounds__(RS_BLOCK) void ransac_pairs_kernel(RsPairs p) {
     const int i = c0 + t;
     const int j = i < Ns ? corr[i] : -1;
     const bool has = (unsigned)j < (unsigned)Nt;
-    const u64 mask = __ballot(has);
-    const int before = __popcll(mask & ((1ull << (t & 63)) - 1ull));
     __syncthreads();                                       // the previous chunk's totals have been read
-    if ((t & 63) == 0) wtot[t >> 6] = __popcll(mask);
-    __syncthreads();
-    int at = base + before;
-    for (int w = 0; w < (t >> 6); ++w) at += wtot[w];
+    int found;
+    const int at = base + wg_rank(has, t, wtot, &found);
     if (has) {                                             // at < Ns: at most one row per source point
       const f32x4 s4 = {sx[i], sx[Ns + i], sx[2 * (size_t)Ns + i], __int_as_float(i)};
       const f32x4 t4 = {tx[j], tx[Nt + j], tx[2 * (size_t)Nt + j], 0.f};
       st4(rows + (size_t)at * 8, s4);
       st4(rows + (size_t)at * 8 + 4, t4);
     }
-    base += ((wtot[0] + wtot[1]) + wtot[2]) + wtot[3];
+    base += found;
   }
   if (t == 0) {
     p.w.M[b] = base;
@@ -267,8 +264,6 @@ __global__ __launch_bounds__(RS_BLOCK) void ransac_best_kernel(RsBest p) {
   if (p.inliers) p.inliers[b] = inl;
 }
 
-inline size_t rs_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct RsPlan { size_t rows, M, nvalid, list, status, pose, count, bytes; };
 
 int rs_plan(const vcr_ransac_args& a, RsPlan* p) {
@@ -282,13 +277,13 @@ int rs_plan(const vcr_ransac_args& a, RsPlan* p) {
     return VCR_EUNSUPPORTED;
   const size_t BT = (size_t)a.B * a.trials;
   p->rows = 0;
-  p->M = rs_up((size_t)a.B * a.Ns * 32);
-  p->nvalid = p->M + rs_up((size_t)a.B * 4);
-  p->list = p->nvalid + rs_up((size_t)a.B * 4);
-  p->status = p->list + rs_up(BT * 4);
-  p->pose = p->status + (a.trial_status ? 0 : rs_up(BT * 4));
-  p->count = p->pose + (a.trial_pose ? 0 : rs_up(BT * 48));
-  p->bytes = p->count + (a.trial_inliers ? 0 : rs_up(BT * 4));
+  p->M = ws_up((size_t)a.B * a.Ns * 32);
+  p->nvalid = p->M + ws_up((size_t)a.B * 4);
+  p->list = p->nvalid + ws_up((size_t)a.B * 4);
+  p->status = p->list + ws_up(BT * 4);
+  p->pose = p->status + (a.trial_status ? 0 : ws_up(BT * 4));
+  p->count = p->pose + (a.trial_pose ? 0 : ws_up(BT * 48));
+  p->bytes = p->count + (a.trial_inliers ? 0 : ws_up(BT * 4));
   return VCR_OK;
 }
 

@@ -246,11 +246,11 @@ static int rf_plan(const vcr_refine_args& a, int cu, int values, RfPlan* p) {
   if (a.max_iterations > VCR_REFINE_MAX_ITERATIONS) return VCR_EUNSUPPORTED;
   const size_t B = (size_t)a.B;
   p->part_off = 2 * p->nn.part_bytes;
-  p->pose_off = p->part_off + nn_up(B * p->nn.nblk * values * sizeof(double));
-  p->prev_off = p->pose_off + nn_up(B * 12 * sizeof(double));
-  p->live_off = p->prev_off + nn_up(B * 2 * sizeof(float));
-  p->iters_off = p->live_off + nn_up(B * sizeof(int));
-  p->bytes = p->iters_off + nn_up(B * sizeof(int));
+  p->pose_off = p->part_off + ws_up(B * p->nn.nblk * values * sizeof(double));
+  p->prev_off = p->pose_off + ws_up(B * 12 * sizeof(double));
+  p->live_off = p->prev_off + ws_up(B * 2 * sizeof(float));
+  p->iters_off = p->live_off + ws_up(B * sizeof(int));
+  p->bytes = p->iters_off + ws_up(B * sizeof(int));
   return VCR_OK;
 }
 
@@ -265,7 +265,7 @@ static int rf_form(const typename Fit::Args* ua, int cu_count, int* queries_per_
   const int e = rf_plan(a, cu_count ? cu_count : vcr_cu_count(), Fit::VALUES, &p);
   if (e) return e;
   if (queries_per_lane) *queries_per_lane = p.nn.Q;
-  if (target_splits) *target_splits = p.nn.S;
+  if (target_splits) *target_splits = p.nn.scan.S;
   return VCR_OK;
 }
 
@@ -304,7 +304,7 @@ static int rf_run(const typename Fit::Args* ua, void* workspace, size_t workspac
   hipLaunchKernelGGL(refine_init_kernel, dim3((unsigned)((a.B + NN_BLOCK - 1) / NN_BLOCK)), dim3(NN_BLOCK), 0, s, in);
   if ((e = VCR_LAUNCH_RC())) return e;
   const RfMerge<Fit> mg{reinterpret_cast<const float*>(w), reinterpret_cast<const int*>(w + nn.part_bytes), a.src, a.tgt, a.R_out, a.t_out,
-                        a.B, a.Ns, a.Nt, nn.S, nn.nblk, a.max_dist * a.max_dist, a.nn_idx, a.nn_d2, part, st.live, fit};
+                        a.B, a.Ns, a.Nt, nn.scan.S, nn.nblk, a.max_dist * a.max_dist, a.nn_idx, a.nn_d2, part, st.live, fit};
   for (int round = 0; round <= a.max_iterations; ++round) {
     if ((e = nn_scan_launch(nn, workspace, st.live, s))) return e;
     hipLaunchKernelGGL(merge_kernel, dim3(nn.merge_grid), dim3(NN_BLOCK), 0, s, mg);

@@ -6,7 +6,7 @@
 // operation: any split of the scan returns the same bits.  A point without a voxel (a non-finite one, every point of a cloud
 // whose grid is too fine) stores VX_NO_KEY and asks for VX_NO_QUERY, which is never stored: it matches nobody, itself included.
 //
-// Seven launches (voxel_plan takes the scan's split from nn_plan; vcr_voxel_args.variant forces it):
+// Seven launches (voxel_plan cuts the scan as nn_plan does, seg_scan.h; vcr_voxel_args.variant forces it):
 //   voxel_bounds_kernel   one workgroup per cloud: min and max over the finite points, the grid's origin in fp64, "too fine"
 //   voxel_keys_kernel     one lane per point: its key
 //   voxel_scan_kernel     256 lanes x one point per lane against one of the S segments of the cloud's own key plane: tiles of
@@ -130,10 +130,8 @@ struct VxScan {
 __global__ __launch_bounds__(NN_BLOCK) void voxel_scan_kernel(VxScan p) {
   __shared__ __attribute__((aligned(16))) u64 lk[NN_TILE];
   const int t = threadIdx.x;
-  const unsigned bid = blockIdx.x;
-  const int s = (int)(bid % (unsigned)p.S);
-  const unsigned rest = bid / (unsigned)p.S;
-  const int blk = (int)(rest % (unsigned)p.nblk), b = (int)(rest / (unsigned)p.nblk);
+  int s, blk, b;
+  seg_workgroup(blockIdx.x, p.S, p.nblk, &s, &blk, &b);
   const int N = p.N;
   const u64* __restrict__ key = p.keys + (size_t)b * N;
   const int i = blk * NN_BLOCK + t;
@@ -142,9 +140,8 @@ __global__ __launch_bounds__(NN_BLOCK) void voxel_scan_kernel(VxScan p) {
   unsigned first = ~0u;                                    // (reads as -1: no match) the lowest matching index: j ascends
   int members = 0;
 
-  const long seg_lo = (long)s * p.seg_len;
-  const int lo = seg_lo < N ? (int)seg_lo : N;
-  const int hi = N - lo < p.seg_len ? N : lo + p.seg_len;              // [lo, hi) is inside [0, N]; empty past the cloud's end
+  int lo, hi;
+  seg_range(s, p.seg_len, N, &lo, &hi);
   for (int t0 = lo; t0 < hi; t0 += NN_TILE) {                          // (workgroup-uniform: the barriers are met by all)
     const int cnt = hi - t0 < NN_TILE ? hi - t0 : NN_TILE;
     const int cnt4 = (cnt + 3) & ~3;                                   // <= NN_TILE
@@ -160,18 +157,6 @@ __global__ __launch_bounds__(NN_BLOCK) void voxel_scan_kernel(VxScan p) {
     p.part_first[at] = (int)first;
     p.part_members[at] = members;
   }
-}
-
-// The number of lanes of the workgroup whose flag is set, and this lane's rank among them (lanes ascending)
-__device__ __forceinline__ int vx_rank(bool flag, int t, int* wcnt, int* total) {
-  const u64 bal = __ballot(flag);
-  const int lane = t & 63, w = t >> 6;
-  if (lane == 0) wcnt[w] = __popcll(bal);
-  __syncthreads();
-  int below = 0, all = 0;
-  for (int k = 0; k < NN_BLOCK / 64; ++k) { below += k < w ? wcnt[k] : 0; all += wcnt[k]; }
-  *total = all;
-  return below + __popcll(bal & ((1ull << lane) - 1ull));
 }
 
 struct VxMerge {
@@ -198,38 +183,18 @@ __global__ __launch_bounds__(NN_BLOCK) void voxel_merge_kernel(VxMerge p) {
     p.members[o] = m;
   }
   int reps;
-  vx_rank(i < p.N && f == i, t, wcnt, &reps);
+  wg_rank(i < p.N && f == i, t, wcnt, &reps);
   if (t == 0) p.blkcnt[(size_t)b * p.nblk + blk] = reps;
 }
 
 __global__ __launch_bounds__(NN_BLOCK) void voxel_offsets_kernel(int* blkcnt, int nblk, VxGrid* grid, int* count) {
   __shared__ int wtot[NN_BLOCK / 64];
-  const int t = threadIdx.x, b = blockIdx.x, lane = t & 63, w = t >> 6;
-  int* cnt = blkcnt + (size_t)b * nblk;                    // in place: a lane reads and writes its own two entries
-  int carry = 0;
-  for (int c0 = 0; c0 < nblk; c0 += 2 * NN_BLOCK) {        // (workgroup-uniform; one round up to 131 072 points)
-    const int i0 = c0 + 2 * t, i1 = i0 + 1;
-    const int a0 = i0 < nblk ? cnt[i0] : 0, a1 = i1 < nblk ? cnt[i1] : 0;
-    int incl = a0 + a1;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(incl, o, 64);
-      incl += lane >= o ? v : 0;
-    }
-    __syncthreads();                                       // the previous round's totals have been read
-    if (lane == 63) wtot[w] = incl;
-    __syncthreads();
-    int below = 0, all = 0;
-    for (int k = 0; k < NN_BLOCK / 64; ++k) { below += k < w ? wtot[k] : 0; all += wtot[k]; }
-    const int excl = carry + below + incl - (a0 + a1);
-    if (i0 < nblk) cnt[i0] = excl;
-    if (i1 < nblk) cnt[i1] = excl + a0;
-    carry += all;
-  }
-  if (t == 0) {
+  const int b = blockIdx.x;
+  const int voxels = wg_offsets(blkcnt + (size_t)b * nblk, nblk, wtot);
+  if (threadIdx.x == 0) {
     const int fine = grid[b].too_fine;
-    grid[b].voxels = carry;                                // (0 when the grid is too fine: no point has a key)
-    count[b] = fine ? -1 : carry;
+    grid[b].voxels = voxels;                               // (0 when the grid is too fine: no point has a key)
+    count[b] = fine ? -1 : voxels;
   }
 }
 
@@ -247,7 +212,7 @@ __global__ __launch_bounds__(NN_BLOCK) void voxel_rank_kernel(VxRank p) {
   const size_t row = (size_t)b * p.N;
   const bool rep = i < p.N && p.first[row + (i < p.N ? i : 0)] == i;
   int reps;
-  const int rank = vx_rank(rep, t, wcnt, &reps);
+  const int rank = wg_rank(rep, t, wcnt, &reps);
   if (rep) {
     const int v = p.blkoff[(size_t)b * p.nblk + blk] + rank;          // < the cloud's voxels <= N
     p.vox[row + i] = v;
@@ -343,12 +308,12 @@ __global__ __launch_bounds__(NN_BLOCK) void voxel_means_kernel(VxMeans p) {
   }
 }
 
-// How one call runs: voxel_plan() validates the arguments, takes the scan's split from nn_plan (B clouds of N points against
-// themselves) and lays out the workspace; the entry points answer from it.
+// How one call runs: voxel_plan() validates the arguments, cuts the scan as nn_plan cuts B clouds of N points against
+// themselves, one point per lane (seg_split under NN_LIMITS), and lays out the workspace; the entry points answer from it.
 struct VxPlan {
   vcr_voxel_args a;
-  int S, seg_len, nblk;
-  unsigned scan_grid, point_grid;
+  SegSplit scan;                                           // (one point per lane: its nblk is the per-point launches' too)
+  unsigned point_grid;
   size_t keys_off, part_off, part_bytes, plane_off, plane_bytes, blk_off, bytes;
 };
 
@@ -358,28 +323,20 @@ static int voxel_plan(const vcr_voxel_args& a, int cu, VxPlan* p) {
   *p = VxPlan{a};
   if (!a.xyz || !a.points || !a.count || a.B < 1) return VCR_EINVAL;
   if (!(a.voxel_size > 0.f) || a.voxel_size == __builtin_huge_valf()) return VCR_EINVAL;     // <= 0, NaN, +inf
-  const int fq = a.variant & 0xF, fs = (a.variant >> 8) & 0xFF;
-  if ((a.variant & ~0xFF0F) || fq > 1 || fs > NN_MAX_SPLITS) return VCR_EINVAL;
+  int fq, fs;
+  if (seg_variant(a.variant, SEG_Q_1, NN_LIMITS, &fq, &fs)) return VCR_EINVAL;
   if (a.N < 1 || a.N > NN_MAX_N || (long)a.B * a.N >= (1L << 31)) return VCR_EUNSUPPORTED;
-  vcr_nn_score_args n{};
-  n.struct_bytes = (uint32_t)sizeof(n);
-  n.src = n.tgt = a.xyz;
-  n.fitness = n.rmse = a.points;                           // (nn_plan only asks that they are given)
-  n.B = a.B; n.Ns = n.Nt = a.N;
-  n.variant = a.variant;
-  NnPlan np;
-  const int e = nn_plan(n, cu, &np);
+  const int e = seg_split(a.B, a.N, a.N, 1, fs, cu, NN_LIMITS, &p->scan);
   if (e) return e;
-  p->S = np.S; p->seg_len = np.seg_len; p->nblk = np.nblk;
-  p->scan_grid = np.scan_grid; p->point_grid = np.merge_grid;
+  p->point_grid = (unsigned)((long)a.B * p->scan.nblk);
   const size_t BN = (size_t)a.B * a.N;
-  p->keys_off = nn_up((size_t)a.B * sizeof(VxGrid));
-  p->part_off = p->keys_off + nn_up(BN * 8);
-  p->part_bytes = nn_up((size_t)np.S * BN * 4);
+  p->keys_off = ws_up((size_t)a.B * sizeof(VxGrid));
+  p->part_off = p->keys_off + ws_up(BN * 8);
+  p->part_bytes = ws_up((size_t)p->scan.S * BN * 4);
   p->plane_off = p->part_off + 2 * p->part_bytes;
-  p->plane_bytes = nn_up(BN * 4);
+  p->plane_bytes = ws_up(BN * 4);
   p->blk_off = p->plane_off + 4 * p->plane_bytes;
-  p->bytes = p->blk_off + nn_up((size_t)a.B * np.nblk * 4);
+  p->bytes = p->blk_off + ws_up((size_t)a.B * p->scan.nblk * 4);
   return VCR_OK;
 }
 
@@ -394,7 +351,7 @@ extern "C" int vcr_voxel_form(const vcr_voxel_args* ua, int cu_count, int* point
   const int e = voxel_plan(a, cu_count ? cu_count : vcr_cu_count(), &p);
   if (e) return e;
   if (points_per_lane) *points_per_lane = 1;
-  if (splits) *splits = p.S;
+  if (splits) *splits = p.scan.S;
   return VCR_OK;
 }
 
@@ -432,21 +389,21 @@ extern "C" int vcr_voxel_f32(const vcr_voxel_args* ua, void* workspace, size_t w
 
   hipLaunchKernelGGL(voxel_bounds_kernel, clouds, block, 0, s, a.xyz, a.N, a.voxel_size, grid);
   if ((e = VCR_LAUNCH_RC())) return e;
-  const VxKeys ky{a.xyz, grid, keys, a.N, p.nblk, a.voxel_size};
+  const VxKeys ky{a.xyz, grid, keys, a.N, p.scan.nblk, a.voxel_size};
   hipLaunchKernelGGL(voxel_keys_kernel, points, block, 0, s, ky);
   if ((e = VCR_LAUNCH_RC())) return e;
-  const VxScan sc{keys, a.B, a.N, p.S, p.seg_len, p.nblk, part_first, part_members};
-  hipLaunchKernelGGL(voxel_scan_kernel, dim3(p.scan_grid), block, 0, s, sc);
+  const VxScan sc{keys, a.B, a.N, p.scan.S, p.scan.seg_len, p.scan.nblk, part_first, part_members};
+  hipLaunchKernelGGL(voxel_scan_kernel, dim3(p.scan.grid), block, 0, s, sc);
   if ((e = VCR_LAUNCH_RC())) return e;
-  const VxMerge mg{part_first, part_members, a.B, a.N, p.S, p.nblk, first, members, blk};
+  const VxMerge mg{part_first, part_members, a.B, a.N, p.scan.S, p.scan.nblk, first, members, blk};
   hipLaunchKernelGGL(voxel_merge_kernel, points, block, 0, s, mg);
   if ((e = VCR_LAUNCH_RC())) return e;
-  hipLaunchKernelGGL(voxel_offsets_kernel, clouds, block, 0, s, blk, p.nblk, grid, a.count);
+  hipLaunchKernelGGL(voxel_offsets_kernel, clouds, block, 0, s, blk, p.scan.nblk, grid, a.count);
   if ((e = VCR_LAUNCH_RC())) return e;
-  const VxRank rk{first, members, blk, a.N, p.nblk, vox, rep_of, a.voxel_points};
+  const VxRank rk{first, members, blk, a.N, p.scan.nblk, vox, rep_of, a.voxel_points};
   hipLaunchKernelGGL(voxel_rank_kernel, points, block, 0, s, rk);
   if ((e = VCR_LAUNCH_RC())) return e;
-  const VxMeans mn{a.xyz, keys, grid, first, members, vox, rep_of, a.N, p.nblk, a.points, a.point_voxel, a.voxel_points};
+  const VxMeans mn{a.xyz, keys, grid, first, members, vox, rep_of, a.N, p.scan.nblk, a.points, a.point_voxel, a.voxel_points};
   hipLaunchKernelGGL(voxel_means_kernel, points, block, 0, s, mn);
   return VCR_LAUNCH_RC();
 }
