@@ -13,7 +13,7 @@ from . import weights, synth  # noqa: F401
 
 __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "score_registration", "refine_registration",
            "estimate_normals", "voxel_down_sample", "remove_statistical_outlier", "remove_radius_outlier", "compute_fpfh_feature",
-           "match_features", "ransac_correspondences", "register_features"]
+           "match_features", "ransac_correspondences", "register_features", "fast_global_registration"]
 
 
 def __getattr__(name):
@@ -45,4 +45,7 @@ def __getattr__(name):
     if name in ("match_features", "ransac_correspondences", "register_features"):
         from . import match
         return getattr(match, name)
+    if name == "fast_global_registration":
+        from .fgr import fast_global_registration
+        return fast_global_registration
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,8 +1,8 @@
 // A pose from correspondences (include/vcr_hip_match.h): Open3D's feature-matching RANSAC with
 // ransac_n = 3, its edge-length and distance checkers, every trial run.  Four launches, no host synchronisation:
-//   ransac_pairs_kernel   one workgroup per cloud: the source points with a partner, ascending, gathered ONCE into contiguous
-//                         32-B rows (sx, sy, sz, source index | tx, ty, tz, 0) by a ballot prefix over chunks of 256; M and a
-//                         zeroed counter of valid trials behind them.
+//   ransac_pairs_kernel   (its body: corr_pairs.h, shared with fgr.hip) one workgroup per cloud: the source points with a partner,
+//                         ascending, gathered ONCE into contiguous 32-B rows (sx, sy, sz, source index | tx, ty, tz, 0) by a
+//                         ballot prefix over chunks of 256; M and a zeroed counter of valid trials behind them.
 //   ransac_trial_kernel   one QUAD per trial: the four lanes draw the same three picks and run the integer and fp32 tests
 //                         together, then the solve of vcr_refine_f32's step with n = 3 -- svd3.h's quad Jacobi and its tail,
 //                         one text for all solves of the library -- the fp32 pose, the distance check of the three picks.  A
@@ -15,16 +15,11 @@
 //                         valid trials -- the highest count, the lowest trial among equals -- and the outputs.
 // Every result is a function of the cloud alone; all writes are plain vector stores.
 #include "seg_scan.h"
+#include "corr_pairs.h"
 #include "svd3.h"
 #include "../../include/vcr_hip_match.h"
 
 namespace {
-
-typedef unsigned long long u64;
-
-constexpr int RS_BLOCK = 256;
-static_assert(RS_BLOCK == WG_BLOCK, "wg_scan.h serves workgroups of this size");
-constexpr int RS_MAX_N = 131072;
 
 struct RsWork {                                            // the workspace, per cloud b
   float* rows;                                             // [B][Ns][8]
@@ -36,47 +31,7 @@ struct RsWork {                                            // the workspace, per
   int* count;                                              // [B][T]
 };
 
-struct RsPairs { const float* src; const float* tgt; const int* corr; int Ns, Nt; RsWork w; int* pairs; };
-
-__global__ __launch_bounds__(RS_BLOCK) void ransac_pairs_kernel(RsPairs p) {
-  __shared__ int wtot[RS_BLOCK / 64];
-  const int t = threadIdx.x, b = blockIdx.x, Ns = p.Ns, Nt = p.Nt;
-  const float* sx = p.src + (size_t)b * 3 * Ns;
-  const float* tx = p.tgt + (size_t)b * 3 * Nt;
-  const int* corr = p.corr + (size_t)b * Ns;
-  float* rows = p.w.rows + (size_t)b * Ns * 8;
-  int base = 0;
-  for (int c0 = 0; c0 < Ns; c0 += RS_BLOCK) {              // (workgroup-uniform: the barriers are met by all)
-    const int i = c0 + t;
-    const int j = i < Ns ? corr[i] : -1;
-    const bool has = (unsigned)j < (unsigned)Nt;
-    __syncthreads();                                       // the previous chunk's totals have been read
-    int found;
-    const int at = base + wg_rank(has, t, wtot, &found);
-    if (has) {                                             // at < Ns: at most one row per source point
-      const f32x4 s4 = {sx[i], sx[Ns + i], sx[2 * (size_t)Ns + i], __int_as_float(i)};
-      const f32x4 t4 = {tx[j], tx[Nt + j], tx[2 * (size_t)Nt + j], 0.f};
-      st4(rows + (size_t)at * 8, s4);
-      st4(rows + (size_t)at * 8 + 4, t4);
-    }
-    base += found;
-  }
-  if (t == 0) {
-    p.w.M[b] = base;
-    p.w.nvalid[b] = 0;
-    if (p.pairs) p.pairs[b] = base;
-  }
-}
-
-__device__ __forceinline__ uint32_t rs_mix32(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return x;
-}
-
-__device__ __forceinline__ float rs_len2(const f32x4& u, const f32x4& v) {
-  const float dx = u[0] - v[0], dy = u[1] - v[1], dz = u[2] - v[2];
-  return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-}
+__global__ __launch_bounds__(RS_BLOCK) void ransac_pairs_kernel(RsPairs p) { rs_pairs_body(p); }
 
 // vcr_hip_score.h's `moved source` and `distance` under the fp32 pose (R row-major, then t)
 __device__ __forceinline__ float rs_d2(const float (&P)[12], float x, float y, float z, float qx, float qy, float qz) {
@@ -109,7 +64,7 @@ __global__ __launch_bounds__(RS_BLOCK) void ransac_trial_kernel(RsTrial p) {
     unsigned at[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      at[j] = (unsigned)(((u64)rs_mix32(p.seed ^ rs_mix32(3u * (unsigned)trial + (unsigned)j)) * (u64)(unsigned)M) >> 32);   // < M
+      at[j] = rs_pick(p.seed, trial, j, M);
       s[j] = ld4(rows + (size_t)at[j] * 8);
       q[j] = ld4(rows + (size_t)at[j] * 8 + 4);
       pick[j] = __float_as_int(s[j][3]);
@@ -318,7 +273,7 @@ extern "C" int vcr_ransac_f32(const vcr_ransac_args* ua, void* workspace, size_t
                   a.trial_inliers ? a.trial_inliers : reinterpret_cast<int*>(w + p.count)};
   const int B = a.B, T = a.trials;
   const float max_d2 = a.max_dist * a.max_dist;            // fp32: one rounding
-  const RsPairs pr{a.src, a.tgt, a.corr, a.Ns, a.Nt, wk, a.pairs};
+  const RsPairs pr{a.src, a.tgt, a.corr, a.Ns, a.Nt, wk.rows, wk.M, wk.nvalid, a.pairs};
   hipLaunchKernelGGL(ransac_pairs_kernel, dim3((unsigned)B), dim3(RS_BLOCK), 0, s, pr);
   if ((e = VCR_LAUNCH_RC())) return e;
   const RsTrial tr{wk, a.Ns, T, a.seed, max_d2, a.similarity * a.similarity, a.similarity != 0.f ? 1 : 0, a.trial_picks};

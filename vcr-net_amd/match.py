@@ -180,7 +180,7 @@ def ransac_correspondences(src, tgt, corr, max_dist, trials=100000, similarity=0
 
 
 def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials=100000, similarity=0.9, seed=0, refine=None,
-                      refine_method="point_to_point", src_normals=None, tgt_normals=None):
+                      refine_method="point_to_point", src_normals=None, tgt_normals=None, method="ransac", fgr=None):
     """Register two clouds of any two sizes with neither a network nor a starting pose: src [B,3,Ns], tgt [B,3,Nt] (float32
     device tensors).  compute_fpfh_feature(k, radius) on both, match_features(mutual), ransac_correspondences(max_dist,
     trials, similarity, seed), then score_registration at max_dist on the FULL clouds (Open3D's closing evaluation).
@@ -189,20 +189,56 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     features' own search).  An estimated normal's SIGN is arbitrary, and the feature of a point changes with it: two copies of
     one surface match far better with normals oriented alike (towards the sensor, say) than with estimated ones -- on the
     test's surface 99.7 % of the one-way matches are the true partner against 18 % at 600 points.
-    Returns a dict: fitness, inlier_rmse, inliers (the score of the RANSAC's pose); R, t, best_trial, pairs and ransac_inliers
-    (the RANSAC's; its `inliers` under that name); corr int32 [B,Ns]; and with refine, `refined`: refine_registration's dict."""
+    method: "ransac", or "fgr": fast_global_registration (``fgr``) takes the RANSAC's place -- no trial
+    budget; trials, similarity and seed are not used, `fgr` is a dict of its keywords (tuple_scale, max_tuples, iterations,
+    division_factor, mu_floor, decrease_mu, tuple_trials, seed).  The score and refine work from its pose in the same way.
+    Returns a dict: fitness, inlier_rmse, inliers (the score of the global pose); R, t, best_trial, pairs and ransac_inliers
+    (the RANSAC's; its `inliers` under that name) -- with "fgr": R, t, pairs, tuples, used, status --; corr int32 [B,Ns]; and
+    with refine, `refined`: refine_registration's dict."""
     from .fpfh import compute_fpfh_feature
     from .refine import refine_registration
     from .score import score_registration
     api = "register_features"
     if refine is not None and not (math.isfinite(float(refine)) and float(refine) >= 0.0):
         raise VcrHipError(f"{api}: refine must be None or a finite correspondence cap >= 0, got {refine}")
+    if method not in ("ransac", "fgr"):
+        raise VcrHipError(f'{api}: method must be "ransac" or "fgr", got {method!r}')
+    if method == "fgr":
+        return _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_method, src_normals, tgt_normals, fgr)
+    if fgr is not None:
+        raise VcrHipError(f'{api}: fgr= holds the keywords of method="fgr"; the method is "ransac"')
     _ransac_checks(api, src, tgt, None, max_dist, trials, similarity, seed, given_corr=False)
     corr = match_features(compute_fpfh_feature(src, src_normals, k=k, radius=radius),
                           compute_fpfh_feature(tgt, tgt_normals, k=k, radius=radius), mutual=mutual)
     r = ransac_correspondences(src, tgt, corr, max_dist, trials, similarity, seed)
     res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist))
     res.update(R=r["R"], t=r["t"], best_trial=r["best_trial"], pairs=r["pairs"], ransac_inliers=r["inliers"], corr=corr)
+    if refine is not None:
+        res["refined"] = refine_registration(src, tgt, r["R"], r["t"], float(refine), method=refine_method)
+    return res
+
+
+def _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_method, src_normals, tgt_normals, kw):
+    """register_features with method="fgr": the same chain with fast_global_registration in the RANSAC's place."""
+    from . import fgr as F
+    from .fpfh import compute_fpfh_feature
+    from .refine import refine_registration
+    from .score import score_registration
+    kw = {} if kw is None else kw
+    if not isinstance(kw, dict) or set(kw) - set(F.DEFAULTS):
+        raise VcrHipError(f"{api}: fgr must be None or a dict with keys among {sorted(F.DEFAULTS)}, got "
+                          f"{sorted(kw) if isinstance(kw, dict) else type(kw).__name__}")
+    kw = dict(F.DEFAULTS, **kw)
+    max_dist = float(max_dist)
+    if not (math.isfinite(max_dist) and max_dist >= 0.0):
+        raise VcrHipError(f"{api}: max_dist must be finite and >= 0, got {max_dist}")
+    F._fgr_checks(api, src, tgt, None, kw["tuple_scale"], kw["max_tuples"], kw["iterations"], kw["division_factor"], kw["mu_floor"],
+                  kw["tuple_trials"], kw["seed"], given_corr=False)
+    corr = match_features(compute_fpfh_feature(src, src_normals, k=k, radius=radius),
+                          compute_fpfh_feature(tgt, tgt_normals, k=k, radius=radius), mutual=mutual)
+    r = F.fast_global_registration(src, tgt, corr, **kw)
+    res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist))
+    res.update(R=r["R"], t=r["t"], pairs=r["pairs"], tuples=r["tuples"], used=r["used"], status=r["status"], corr=corr)
     if refine is not None:
         res["refined"] = refine_registration(src, tgt, r["R"], r["t"], float(refine), method=refine_method)
     return res
