@@ -13,7 +13,8 @@ from . import weights, synth  # noqa: F401
 
 __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "score_registration", "refine_registration",
            "estimate_normals", "voxel_down_sample", "remove_statistical_outlier", "remove_radius_outlier", "compute_fpfh_feature",
-           "match_features", "ransac_correspondences", "register_features", "fast_global_registration"]
+           "match_features", "ransac_correspondences", "register_features", "fast_global_registration", "centred",
+           "uncentred_pose"]
 
 
 def __getattr__(name):
@@ -48,4 +49,7 @@ def __getattr__(name):
     if name == "fast_global_registration":
         from .fgr import fast_global_registration
         return fast_global_registration
+    if name in ("centred", "uncentred_pose"):
+        from . import centre
+        return getattr(centre, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -92,7 +92,8 @@ def compute_fpfh_feature(xyz, normals=None, k=30, radius=None, want_normals=Fals
     than it (Open3D's hybrid search with max_nn = k + 1).  1 <= k <= 62 and k + 1 <= N.
     The neighbours are the library's kNN (native.knn on the points' rows, ties broken exactly), whose distance is the expansion
     2 x.y - |x|^2 - |y|^2 in fp32: for a cloud far from the origin relative to its spacing it cancels, and the neighbours are
-    then not the nearest.  Centre such a cloud first (the features do not change under a translation)."""
+    then not the nearest.  Centre such a cloud first (the features do not change under a translation):
+    ``vcrnet_amd.centred(xyz)`` returns xyz - c and the centre c it took."""
     api = "compute_fpfh_feature"
     extension.check_cloud(api, "xyz", xyz)
     k = int(k)

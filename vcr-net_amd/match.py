@@ -180,7 +180,8 @@ def ransac_correspondences(src, tgt, corr, max_dist, trials=100000, similarity=0
 
 
 def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials=100000, similarity=0.9, seed=0, refine=None,
-                      refine_method="point_to_point", src_normals=None, tgt_normals=None, method="ransac", fgr=None):
+                      refine_method="point_to_point", src_normals=None, tgt_normals=None, method="ransac", fgr=None,
+                      centre=False):
     """Register two clouds of any two sizes with neither a network nor a starting pose: src [B,3,Ns], tgt [B,3,Nt] (float32
     device tensors).  compute_fpfh_feature(k, radius) on both, match_features(mutual), ransac_correspondences(max_dist,
     trials, similarity, seed), then score_registration at max_dist on the FULL clouds (Open3D's closing evaluation).
@@ -194,7 +195,17 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     division_factor, mu_floor, decrease_mu, tuple_trials, seed).  The score and refine work from its pose in the same way.
     Returns a dict: fitness, inlier_rmse, inliers (the score of the global pose); R, t, best_trial, pairs and ransac_inliers
     (the RANSAC's; its `inliers` under that name) -- with "fgr": R, t, pairs, tuples, used, status --; corr int32 [B,Ns]; and
-    with refine, `refined`: refine_registration's dict."""
+    with refine, `refined`: refine_registration's dict.
+    centre: False works in the caller's frame; True, or a pair (c_src, c_tgt) of [B,3] tensors, runs the whole chain --
+    features, matching, RANSAC or FGR, score and refine -- on the clouds moved each to its own centre (``centred``), carries every
+    pose back (``uncentred_pose``) and takes every score on the caller's clouds.  For clouds far from the origin relative to their
+    extent: the features' and the normals' search cancels there in fp32.  ransac_inliers stays the
+    RANSAC's own count."""
+    if centre is not False and centre is not None:
+        return _register_centred(src, tgt, max_dist, centre, refine,
+                                 dict(k=k, radius=radius, mutual=mutual, trials=trials, similarity=similarity, seed=seed,
+                                      refine=refine, refine_method=refine_method, src_normals=src_normals,
+                                      tgt_normals=tgt_normals, method=method, fgr=fgr))
     from .fpfh import compute_fpfh_feature
     from .refine import refine_registration
     from .score import score_registration
@@ -241,4 +252,21 @@ def _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_met
     res.update(R=r["R"], t=r["t"], pairs=r["pairs"], tuples=r["tuples"], used=r["used"], status=r["status"], corr=corr)
     if refine is not None:
         res["refined"] = refine_registration(src, tgt, r["R"], r["t"], float(refine), method=refine_method)
+    return res
+
+
+def _register_centred(src, tgt, max_dist, centre, refine, kw):
+    """register_features(centre=...): the chain on the centred clouds, the poses and scores in the caller's frame."""
+    from .centre import take_centres, uncentred_pose
+    from .refine import uncentre_refined
+    from .score import score_registration
+    api = "register_features"
+    extension.check_cloud(api, "src", src)
+    extension.check_cloud(api, "tgt", tgt)
+    src_c, c_src, tgt_c, c_tgt = take_centres(api, centre, src, tgt)
+    res = register_features(src_c, tgt_c, max_dist, centre=False, **kw)
+    _, res["t"] = uncentred_pose(res["R"], res["t"], c_src, c_tgt)
+    res.update(score_registration(src, tgt, res["R"], res["t"], float(max_dist)))
+    if "refined" in res:
+        res["refined"] = uncentre_refined(res["refined"], src, tgt, c_src, c_tgt, float(refine))
     return res

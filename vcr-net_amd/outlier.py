@@ -145,7 +145,8 @@ def remove_statistical_outlier(xyz, nb_neighbors=20, std_ratio=2.0):
     does not enter the statistics.
     The neighbours are the library's kNN (native.knn on the points' rows, ties broken exactly), whose distance is the expansion
     2 x.y - |x|^2 - |y|^2 in fp32: for a cloud far from the origin relative to its spacing it cancels, and the neighbours are
-    then not the nearest.  Centre such a cloud first (the filter does not change under a translation)."""
+    then not the nearest.  Centre such a cloud first (the filter does not change under a translation):
+    ``vcrnet_amd.centred(xyz)`` returns xyz - c and the centre c it took."""
     api = "remove_statistical_outlier"
     extension.check_cloud(api, "xyz", xyz)
     _on_device(api, xyz)

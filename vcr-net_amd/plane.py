@@ -76,7 +76,8 @@ def estimate_normals(xyz, k=20, viewpoint=None, want_curvature=False, want_idx=F
     No orientation is propagated between points.
     The neighbours are the library's kNN (native.knn on the points' rows, ties broken exactly), whose distance is the expansion
     2 x.y - |x|^2 - |y|^2 in fp32: for a cloud far from the origin relative to its spacing it cancels, and the neighbours are
-    then not the nearest.  Centre such a cloud first (normals do not change under a translation)."""
+    then not the nearest.  Centre such a cloud first (normals do not change under a translation):
+    ``vcrnet_amd.centred(xyz)`` returns xyz - c and the centre c it took."""
     if not torch.is_tensor(xyz) or xyz.dim() != 3 or xyz.shape[1] != 3:
         raise VcrHipError(f"estimate_normals: xyz must be a [B, 3, N] point cloud, got "
                           f"{tuple(xyz.shape) if torch.is_tensor(xyz) else type(xyz).__name__}")

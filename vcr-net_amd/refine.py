@@ -103,7 +103,8 @@ METHODS = ("point_to_point", "point_to_plane", "generalized")
 
 
 def refine_registration(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6,
-                        want_nn=False, method="point_to_point", tgt_normals=None, normal_k=20, src_normals=None, epsilon=1e-3):
+                        want_nn=False, method="point_to_point", tgt_normals=None, normal_k=20, src_normals=None, epsilon=1e-3,
+                        centre=False):
     """Improve the pose (R, t) on the FULL clouds: src [B,3,Ns], tgt [B,3,Nt] (Ns != Nt allowed, each up to 131 072 points;
     device tensors).  An ICP: every round matches each moved source point to its nearest target point, keeps the pairs within
     max_dist and solves the best rigid update for them; a cloud stops on its own when fitness and inlier RMSE both change by
@@ -121,11 +122,23 @@ def refine_registration(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=3
       fitness, inlier_rmse, inliers           of the refined pose, exactly score_registration(src, tgt, R, t, max_dist)'s
       iterations     int32 [B]                updates applied;  converged  int32 [B]: 1 = stopped by the rel_* test
       nn_idx, nn_d2 (want_nn)                 int64 / float32 [B,Ns], as score_registration's
-    R = t = None: start from the identity."""
+    R = t = None: start from the identity.
+    centre: False works in the caller's frame.  The six-unknown fits ("point_to_plane", "generalized") turn about the frame's
+    origin, and estimate_normals' search cancels in fp32 far from it: on a cloud whose distance from the origin is a hundred
+    times its extent they lose every inlier from a start a few degrees off.  True moves the source and
+    the target each to its own centre first (``centred``: the mean of the finite coordinates), a pair (c_src, c_tgt) of [B,3]
+    tensors to the centres given -- before anything else, the normals estimated inside included --, runs the method there,
+    carries R, t, R_ba, t_ba back (``uncentred_pose``) and takes fitness, inlier_rmse, inliers, nn_idx and nn_d2 from the
+    caller's clouds at the returned pose."""
     if method not in METHODS:
         raise VcrHipError(f"refine_registration: method must be one of {METHODS}, got {method!r}")
     if method != "generalized" and (src_normals is not None or epsilon != 1e-3):
         raise VcrHipError("refine_registration: src_normals and epsilon are read by method='generalized' only")
+    if centre is not False and centre is not None:
+        extension.check_pair("refine_registration", src, tgt, R, t)
+        return _refine_centred(src, tgt, R, t, max_dist, centre, want_nn,
+                               dict(max_iterations=max_iterations, rel_fitness=rel_fitness, rel_rmse=rel_rmse, method=method,
+                                    tgt_normals=tgt_normals, normal_k=normal_k, src_normals=src_normals, epsilon=epsilon))
     if method == "generalized":
         from . import gicp, plane
         _cloud("src", src)
@@ -153,3 +166,29 @@ def refine_registration(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=3
     if want_nn:
         res["nn_idx"], res["nn_d2"] = f["nn_idx"].long(), f["nn_d2"]
     return res
+
+
+def uncentre_refined(res, src, tgt, c_src, c_tgt, max_dist, want_nn=False):
+    """refine_registration's dict from clouds centred at c_src, c_tgt -> the same in the caller's frame: the poses carried back,
+    the evaluation taken again on the caller's clouds (src, tgt) at the pose returned."""
+    from .centre import uncentred_pose
+    from .score import score_registration
+    out = dict(res)
+    _, out["t"] = uncentred_pose(res["R"], res["t"], c_src, c_tgt)
+    _, out["t_ba"] = uncentred_pose(res["R_ba"], res["t_ba"], c_tgt, c_src)
+    out.update(score_registration(src, tgt, out["R"], out["t"], max_dist, want_nn=want_nn))
+    return out
+
+
+def _refine_centred(src, tgt, R, t, max_dist, centre, want_nn, kw):
+    from .centre import centred_pose, take_centres
+    src_c, c_src, tgt_c, c_tgt = take_centres("refine_registration", centre, src, tgt)
+    if R is not None:
+        native.same_device(src, tgt, R, t)
+        if tuple(R.shape) != (src.shape[0], 3, 3) or tuple(t.shape) != (src.shape[0], 3):
+            raise VcrHipError(f"refine_registration: R must be [B, 3, 3] and t [B, 3] with B = {src.shape[0]}, got "
+                              f"{tuple(R.shape)} and {tuple(t.shape)}")
+        R, t = R.contiguous().float(), t.contiguous().float()
+    R_c, t_c = centred_pose(R, t, c_src, c_tgt)
+    res = refine_registration(src_c, tgt_c, R_c, t_c, max_dist, want_nn=False, centre=False, **kw)
+    return uncentre_refined(res, src, tgt, c_src, c_tgt, max_dist, want_nn)
