@@ -14,7 +14,7 @@ from . import weights, synth  # noqa: F401
 __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "score_registration", "refine_registration",
            "estimate_normals", "voxel_down_sample", "remove_statistical_outlier", "remove_radius_outlier", "compute_fpfh_feature",
            "match_features", "ransac_correspondences", "register_features", "fast_global_registration", "centred",
-           "uncentred_pose"]
+           "uncentred_pose", "search_knn"]
 
 
 def __getattr__(name):
@@ -49,6 +49,9 @@ def __getattr__(name):
     if name == "fast_global_registration":
         from .fgr import fast_global_registration
         return fast_global_registration
+    if name == "search_knn":
+        from .grid import search_knn
+        return search_knn
     if name in ("centred", "uncentred_pose"):
         from . import centre
         return getattr(centre, name)

@@ -10,7 +10,7 @@ import ctypes as C
 import math
 import torch
 
-from . import extension, native, plane
+from . import extension, grid, native, plane
 from .native import VcrHipError, f32p, ptr
 from .score import i32p
 
@@ -82,7 +82,7 @@ def fpfh(xyz4, idx, spfh, radius=0.0, guard=0, prefill=None):
     return (feat, raw) if guard or prefill is not None else feat
 
 
-def compute_fpfh_feature(xyz, normals=None, k=30, radius=None, want_normals=False, want_idx=False):
+def compute_fpfh_feature(xyz, normals=None, k=30, radius=None, want_normals=False, want_idx=False, search="knn"):
     """The 33-bin Fast Point Feature Histogram of every point of xyz [B,3,N] (device tensor, up to 131 072 points a cloud) from
     its k nearest neighbours: Open3D's compute_fpfh_feature, in fp64 on the device.  Returns float32 [B,33,N] -- three groups
     of 11 bins, each group of a point summing to 200 where the point and a neighbour have pairs to count; with want_normals
@@ -93,9 +93,13 @@ def compute_fpfh_feature(xyz, normals=None, k=30, radius=None, want_normals=Fals
     The neighbours are the library's kNN (native.knn on the points' rows, ties broken exactly), whose distance is the expansion
     2 x.y - |x|^2 - |y|^2 in fp32: for a cloud far from the origin relative to its spacing it cancels, and the neighbours are
     then not the nearest.  Centre such a cloud first (the features do not change under a translation):
-    ``vcrnet_amd.centred(xyz)`` returns xyz - c and the centre c it took."""
+    ``vcrnet_amd.centred(xyz)`` returns xyz - c and the centre c it took.
+    search: "knn" is that search.  "grid" takes the neighbours (the normals' too) from ``search_knn``
+    instead: distances of differences, so no centring is needed, and the point itself excluded by its index.  The faster one
+    for large clouds."""
     api = "compute_fpfh_feature"
     extension.check_cloud(api, "xyz", xyz)
+    grid.check_search(api, search)
     k = int(k)
     B, _, N = xyz.shape
     if k < 1 or k > MAX_K:
@@ -114,12 +118,12 @@ def compute_fpfh_feature(xyz, normals=None, k=30, radius=None, want_normals=Fals
                           "(there is no CPU fallback by design)")
     r = 0.0 if radius is None else radius
     if normals is None:
-        normals, idx = plane.estimate_normals(xyz, k, want_idx=True)          # its search is this call's
+        normals, idx = plane.estimate_normals(xyz, k, want_idx=True, search=search)   # its search is this call's
         xyz4 = native.to_rows4(xyz)
     else:
         normals = normals.contiguous().float()
         xyz4 = native.to_rows4(xyz)
-        idx = native.knn(xyz4, None, k)
+        idx = native.knn(xyz4, None, k) if search == "knn" else grid.search_knn(xyz, k)
     feat = fpfh(xyz4, idx, spfh(xyz4, normals, idx, r), r)
     res = (feat,) + ((normals,) if want_normals else ()) + ((idx,) if want_idx else ())
     return res[0] if len(res) == 1 else res

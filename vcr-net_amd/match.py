@@ -181,7 +181,7 @@ def ransac_correspondences(src, tgt, corr, max_dist, trials=100000, similarity=0
 
 def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials=100000, similarity=0.9, seed=0, refine=None,
                       refine_method="point_to_point", src_normals=None, tgt_normals=None, method="ransac", fgr=None,
-                      centre=False):
+                      centre=False, search="knn"):
     """Register two clouds of any two sizes with neither a network nor a starting pose: src [B,3,Ns], tgt [B,3,Nt] (float32
     device tensors).  compute_fpfh_feature(k, radius) on both, match_features(mutual), ransac_correspondences(max_dist,
     trials, similarity, seed), then score_registration at max_dist on the FULL clouds (Open3D's closing evaluation).
@@ -200,12 +200,17 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     features, matching, RANSAC or FGR, score and refine -- on the clouds moved each to its own centre (``centred``), carries every
     pose back (``uncentred_pose``) and takes every score on the caller's clouds.  For clouds far from the origin relative to their
     extent: the features' and the normals' search cancels there in fp32.  ransac_inliers stays the
-    RANSAC's own count."""
+    RANSAC's own count.
+    search: handed to both compute_fpfh_feature calls: "knn" is the brute-force search on the points' rows, "grid" takes the
+    features' and the normals' neighbours from ``search_knn`` -- distances of differences, so the
+    features need no centring, and a point excluded from its own row by its index."""
+    from . import grid
+    grid.check_search("register_features", search)
     if centre is not False and centre is not None:
         return _register_centred(src, tgt, max_dist, centre, refine,
                                  dict(k=k, radius=radius, mutual=mutual, trials=trials, similarity=similarity, seed=seed,
                                       refine=refine, refine_method=refine_method, src_normals=src_normals,
-                                      tgt_normals=tgt_normals, method=method, fgr=fgr))
+                                      tgt_normals=tgt_normals, method=method, fgr=fgr, search=search))
     from .fpfh import compute_fpfh_feature
     from .refine import refine_registration
     from .score import score_registration
@@ -215,12 +220,12 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     if method not in ("ransac", "fgr"):
         raise VcrHipError(f'{api}: method must be "ransac" or "fgr", got {method!r}')
     if method == "fgr":
-        return _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_method, src_normals, tgt_normals, fgr)
+        return _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_method, src_normals, tgt_normals, fgr, search)
     if fgr is not None:
         raise VcrHipError(f'{api}: fgr= holds the keywords of method="fgr"; the method is "ransac"')
     _ransac_checks(api, src, tgt, None, max_dist, trials, similarity, seed, given_corr=False)
-    corr = match_features(compute_fpfh_feature(src, src_normals, k=k, radius=radius),
-                          compute_fpfh_feature(tgt, tgt_normals, k=k, radius=radius), mutual=mutual)
+    corr = match_features(compute_fpfh_feature(src, src_normals, k=k, radius=radius, search=search),
+                          compute_fpfh_feature(tgt, tgt_normals, k=k, radius=radius, search=search), mutual=mutual)
     r = ransac_correspondences(src, tgt, corr, max_dist, trials, similarity, seed)
     res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist))
     res.update(R=r["R"], t=r["t"], best_trial=r["best_trial"], pairs=r["pairs"], ransac_inliers=r["inliers"], corr=corr)
@@ -229,7 +234,7 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     return res
 
 
-def _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_method, src_normals, tgt_normals, kw):
+def _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_method, src_normals, tgt_normals, kw, search="knn"):
     """register_features with method="fgr": the same chain with fast_global_registration in the RANSAC's place."""
     from . import fgr as F
     from .fpfh import compute_fpfh_feature
@@ -245,8 +250,8 @@ def _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_met
         raise VcrHipError(f"{api}: max_dist must be finite and >= 0, got {max_dist}")
     F._fgr_checks(api, src, tgt, None, kw["tuple_scale"], kw["max_tuples"], kw["iterations"], kw["division_factor"], kw["mu_floor"],
                   kw["tuple_trials"], kw["seed"], given_corr=False)
-    corr = match_features(compute_fpfh_feature(src, src_normals, k=k, radius=radius),
-                          compute_fpfh_feature(tgt, tgt_normals, k=k, radius=radius), mutual=mutual)
+    corr = match_features(compute_fpfh_feature(src, src_normals, k=k, radius=radius, search=search),
+                          compute_fpfh_feature(tgt, tgt_normals, k=k, radius=radius, search=search), mutual=mutual)
     r = F.fast_global_registration(src, tgt, corr, **kw)
     res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist))
     res.update(R=r["R"], t=r["t"], pairs=r["pairs"], tuples=r["tuples"], used=r["used"], status=r["status"], corr=corr)

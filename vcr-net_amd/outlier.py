@@ -12,7 +12,7 @@ import math
 import operator
 import torch
 
-from . import extension, native
+from . import extension, grid, native
 from .native import VcrHipError, f32p, ptr
 from .score import f64p, i32p
 
@@ -132,7 +132,7 @@ def radius_filter(xyz, radius, nb_points, variant=0, want_trace=True, guard=0, p
     return o
 
 
-def remove_statistical_outlier(xyz, nb_neighbors=20, std_ratio=2.0):
+def remove_statistical_outlier(xyz, nb_neighbors=20, std_ratio=2.0, search="knn"):
     """xyz [B,3,N] (device tensor, up to 131 072 points a cloud) without the points whose mean distance to their nb_neighbors
     nearest points (the point itself among them, as Open3D counts) lies more than std_ratio standard deviations above the
     cloud's mean of those distances: Open3D's remove_statistical_outlier, in fp64 on the device.  A point AT the threshold is
@@ -146,9 +146,13 @@ def remove_statistical_outlier(xyz, nb_neighbors=20, std_ratio=2.0):
     The neighbours are the library's kNN (native.knn on the points' rows, ties broken exactly), whose distance is the expansion
     2 x.y - |x|^2 - |y|^2 in fp32: for a cloud far from the origin relative to its spacing it cancels, and the neighbours are
     then not the nearest.  Centre such a cloud first (the filter does not change under a translation):
-    ``vcrnet_amd.centred(xyz)`` returns xyz - c and the centre c it took."""
+    ``vcrnet_amd.centred(xyz)`` returns xyz - c and the centre c it took.
+    search: "knn" is that search.  "grid" takes the nb_neighbors - 1 other points from ``search_knn``
+    instead: distances of differences, so no centring is needed, and the point itself excluded by its index.  The faster one
+    for large clouds."""
     api = "remove_statistical_outlier"
     extension.check_cloud(api, "xyz", xyz)
+    grid.check_search(api, search)
     _on_device(api, xyz)
     if _integer(nb_neighbors) is None or not 2 <= nb_neighbors <= MAX_K + 1:
         raise VcrHipError(f"{api}: nb_neighbors must be an integer in [2, {MAX_K + 1}], got {nb_neighbors}")
@@ -159,7 +163,8 @@ def remove_statistical_outlier(xyz, nb_neighbors=20, std_ratio=2.0):
     if not (math.isfinite(std_ratio) and std_ratio >= 0.0):
         raise VcrHipError(f"{api}: std_ratio must be finite and >= 0, got {std_ratio}")
     xyz4 = native.to_rows4(xyz)
-    idx = native.knn(xyz4, None, int(nb_neighbors) - 1)
+    k = int(nb_neighbors) - 1
+    idx = native.knn(xyz4, None, k) if search == "knn" else grid.search_knn(xyz, k)
     o = stat_filter(xyz4, idx, std_ratio, want_trace=False)
     return o["points"], o["count"], o["index"]
 

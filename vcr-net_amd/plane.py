@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import torch
 
-from . import extension, native, refine
+from . import extension, grid, native, refine
 from .native import VcrHipError, f32p, ptr
 from .score import i32p
 
@@ -67,7 +67,7 @@ def normals(xyz4, idx, viewpoint=None, want_curvature=True, guard=0, prefill=Non
     return (nrm, cur, raw) if guard or prefill is not None else (nrm, cur)
 
 
-def estimate_normals(xyz, k=20, viewpoint=None, want_curvature=False, want_idx=False):
+def estimate_normals(xyz, k=20, viewpoint=None, want_curvature=False, want_idx=False, search="knn"):
     """A unit normal per point of xyz [B,3,N] (device tensor) from its k nearest neighbours: the eigenvector of the smallest
     eigenvalue of the covariance of the point and those neighbours (Open3D's estimate_normals with a kNN search), in fp64 on
     the device.  Returns normals float32 [B,3,N]; with want_curvature also the surface variation lambda0 / (lambda0 + lambda1 +
@@ -77,10 +77,14 @@ def estimate_normals(xyz, k=20, viewpoint=None, want_curvature=False, want_idx=F
     The neighbours are the library's kNN (native.knn on the points' rows, ties broken exactly), whose distance is the expansion
     2 x.y - |x|^2 - |y|^2 in fp32: for a cloud far from the origin relative to its spacing it cancels, and the neighbours are
     then not the nearest.  Centre such a cloud first (normals do not change under a translation):
-    ``vcrnet_amd.centred(xyz)`` returns xyz - c and the centre c it took."""
+    ``vcrnet_amd.centred(xyz)`` returns xyz - c and the centre c it took.
+    search: "knn" is that search.  "grid" takes the neighbours from ``search_knn`` instead: distances
+    of differences, so no centring is needed, and the point itself excluded by its index (among copies of a point the brute
+    force drops whichever of them came first).  The faster one for large clouds."""
     if not torch.is_tensor(xyz) or xyz.dim() != 3 or xyz.shape[1] != 3:
         raise VcrHipError(f"estimate_normals: xyz must be a [B, 3, N] point cloud, got "
                           f"{tuple(xyz.shape) if torch.is_tensor(xyz) else type(xyz).__name__}")
+    grid.check_search("estimate_normals", search)
     if not xyz.is_cuda:
         raise VcrHipError("estimate_normals runs on the MI355X HIP path only; move the cloud to cuda "
                           "(there is no CPU fallback by design)")
@@ -94,7 +98,7 @@ def estimate_normals(xyz, k=20, viewpoint=None, want_curvature=False, want_idx=F
                                   or not viewpoint.is_cuda):
         raise VcrHipError(f"estimate_normals: viewpoint must be a device tensor [B, 3] with B = {xyz.shape[0]}")
     xyz4 = native.to_rows4(xyz)
-    idx = native.knn(xyz4, None, k)
+    idx = native.knn(xyz4, None, k) if search == "knn" else grid.search_knn(xyz, k)
     nrm, cur = normals(xyz4, idx, viewpoint, want_curvature=want_curvature)
     res = (nrm,) + ((cur,) if want_curvature else ()) + ((idx,) if want_idx else ())
     return res[0] if len(res) == 1 else res
