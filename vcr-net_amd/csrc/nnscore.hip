@@ -20,6 +20,7 @@
 // The geometry of the last two depends on Ns alone, so every form of the first returns the same bits.  No atomics.  The scan's
 // frame (seg_scan.h) and the two reductions (wg_scan.h) are the ones every scan of the library uses.
 #include "nn_scan.h"
+#include "grid_nn.h"
 
 namespace {
 
@@ -96,6 +97,22 @@ extern "C" size_t vcr_nn_score_workspace_bytes(const vcr_nn_score_args* ua, int 
   return nn_plan(a, cu_count ? cu_count : vcr_cu_count(), &p) ? 0 : p.bytes;
 }
 
+// The merge and the final reduction behind a search that has filled the workspace's candidates
+static int nn_finish(const NnPlan& p, void* workspace, hipStream_t s) {
+  const vcr_nn_score_args& a = p.a;
+  unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
+  float* part_d2 = reinterpret_cast<float*>(w);
+  int* part_idx = reinterpret_cast<int*>(w + p.part_bytes);
+  NnPartial* partial = reinterpret_cast<NnPartial*>(w + p.partial_off);
+  const NnMerge mg{part_d2, part_idx, a.B, a.Ns, p.scan.S, p.nblk, a.max_dist * a.max_dist, a.nn_idx, a.nn_d2, partial};
+  hipLaunchKernelGGL(nn_merge_kernel, dim3(p.merge_grid), dim3(NN_BLOCK), 0, s, mg);
+  int e;
+  if ((e = VCR_LAUNCH_RC())) return e;
+  const NnFinal fin{partial, a.Ns, p.nblk, a.inliers, a.sum_d2, a.fitness, a.rmse};
+  hipLaunchKernelGGL(nn_final_kernel, dim3((unsigned)a.B), dim3(NN_BLOCK), 0, s, fin);
+  return VCR_LAUNCH_RC();
+}
+
 extern "C" int vcr_nn_score_f32(const vcr_nn_score_args* ua, void* workspace, size_t workspace_bytes, vcr_stream_t stream) {
   vcr_nn_score_args a;
   if (nn_take(ua, &a)) return VCR_EINVAL;
@@ -109,15 +126,57 @@ extern "C" int vcr_nn_score_f32(const vcr_nn_score_args* ua, void* workspace, si
   if (e) return e;
   if (workspace_bytes < p.bytes) return VCR_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
-  float* part_d2 = reinterpret_cast<float*>(w);
-  int* part_idx = reinterpret_cast<int*>(w + p.part_bytes);
-  NnPartial* partial = reinterpret_cast<NnPartial*>(w + p.partial_off);
   if ((e = nn_scan_launch(p, workspace, nullptr, s))) return e;
-  const NnMerge mg{part_d2, part_idx, a.B, a.Ns, p.scan.S, p.nblk, a.max_dist * a.max_dist, a.nn_idx, a.nn_d2, partial};
-  hipLaunchKernelGGL(nn_merge_kernel, dim3(p.merge_grid), dim3(NN_BLOCK), 0, s, mg);
-  if ((e = VCR_LAUNCH_RC())) return e;
-  const NnFinal fin{partial, a.Ns, p.nblk, a.inliers, a.sum_d2, a.fitness, a.rmse};
-  hipLaunchKernelGGL(nn_final_kernel, dim3((unsigned)a.B), dim3(NN_BLOCK), 0, s, fin);
-  return VCR_LAUNCH_RC();
+  return nn_finish(p, workspace, s);
+}
+
+// ------------------------------------------------------------------------- the grid sibling (include/vcr_hip_gridnn.h, 4.20)
+
+// The scan's plan at one target split -- the merge then folds the grid search's one candidate a point -- and the grid's behind
+// its workspace.  No device is asked: neither plan depends on one.
+static int nn_grid_plan(const vcr_nn_score_args* ua, const vcr_grid_nn_args* ug, NnPlan* p, GridNnPlan* g) {
+  vcr_nn_score_args a;
+  if (nn_take(ua, &a) || !ug || a.variant != 0) return VCR_EINVAL;
+  a.variant = VCR_NN_SCORE_VARIANT(1, 1);
+  int e = nn_plan(a, 1, p);
+  if (e) return e;
+  return gridnn_plan(ug, GRIDNN_SCORE, 1, a.B, a.Ns, a.Nt, g);
+}
+
+extern "C" int vcr_nn_score_grid_form(const vcr_nn_score_args* ua, const vcr_grid_nn_args* ug, int cu_count, int* cells_per_cloud,
+                                      int* order, int* queries_per_workgroup) {
+  NnPlan p;
+  GridNnPlan g;
+  if (cu_count < 0) return VCR_EINVAL;
+  const int e = nn_grid_plan(ua, ug, &p, &g);
+  if (e) return e;
+  if (cells_per_cloud) *cells_per_cloud = g.cells;
+  if (order) *order = g.order;
+  if (queries_per_workgroup) *queries_per_workgroup = VCR_GRID_QUERIES;
+  return VCR_OK;
+}
+
+extern "C" size_t vcr_nn_score_grid_workspace_bytes(const vcr_nn_score_args* ua, const vcr_grid_nn_args* ug, int cu_count) {
+  NnPlan p;
+  GridNnPlan g;
+  if (cu_count < 0 || nn_grid_plan(ua, ug, &p, &g)) return 0;
+  return p.bytes + g.bytes;
+}
+
+extern "C" int vcr_nn_score_grid_f32(const vcr_nn_score_args* ua, const vcr_grid_nn_args* ug, void* workspace, size_t workspace_bytes,
+                                     vcr_stream_t stream) {
+  NnPlan p;
+  GridNnPlan g;
+  int e = nn_grid_plan(ua, ug, &p, &g);
+  if (e) return e;
+  if (!workspace || (((uintptr_t)workspace) & 15)) return VCR_EINVAL;
+  if (workspace_bytes < p.bytes + g.bytes) return VCR_EWORKSPACE;
+  vcr_stream_scope scope_(stream);
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
+  const vcr_nn_score_args& a = p.a;
+  if ((e = gridnn_build(g, a.src, a.tgt, w + p.bytes, s))) return e;
+  if ((e = gridnn_search(g, a.src, a.R, a.t, a.max_dist * a.max_dist, w + p.bytes, reinterpret_cast<float*>(w),
+                         reinterpret_cast<int*>(w + p.part_bytes), nullptr, s))) return e;
+  return nn_finish(p, workspace, s);
 }

@@ -91,5 +91,21 @@ extern "C" int vcr_refine_form(const vcr_refine_args* ua, int cu_count, int* que
 extern "C" size_t vcr_refine_workspace_bytes(const vcr_refine_args* ua, int cu_count) { return rf_workspace_bytes<PointFit>(ua, cu_count); }
 
 extern "C" int vcr_refine_f32(const vcr_refine_args* ua, void* workspace, size_t workspace_bytes, vcr_stream_t stream) {
-  return rf_run<PointFit>(ua, workspace, workspace_bytes, stream, refine_merge_kernel, refine_cloud_kernel);
+  return rf_run<PointFit>(ua, nullptr, workspace, workspace_bytes, stream, refine_merge_kernel, refine_cloud_kernel);
+}
+
+// The grid siblings (include/vcr_hip_gridnn.h): the same loop behind another search
+extern "C" int vcr_refine_grid_form(const vcr_refine_args* ua, const vcr_grid_nn_args* ug, int cu_count, int* cells_per_cloud, int* order,
+                                    int* queries_per_workgroup) {
+  return rf_grid_form<PointFit>(ua, ug, cu_count, cells_per_cloud, order, queries_per_workgroup);
+}
+
+extern "C" size_t vcr_refine_grid_workspace_bytes(const vcr_refine_args* ua, const vcr_grid_nn_args* ug, int cu_count) {
+  return rf_grid_workspace_bytes<PointFit>(ua, ug, cu_count);
+}
+
+extern "C" int vcr_refine_grid_f32(const vcr_refine_args* ua, const vcr_grid_nn_args* ug, void* workspace, size_t workspace_bytes,
+                                   vcr_stream_t stream) {
+  if (!ug) return VCR_EINVAL;
+  return rf_run<PointFit>(ua, ug, workspace, workspace_bytes, stream, refine_merge_kernel, refine_cloud_kernel);
 }

@@ -18,6 +18,7 @@
 // The kernels themselves stay in the fits' .hip files under their own names, as wrappers of the bodies below.
 #pragma once
 #include "nn_scan.h"
+#include "grid_nn.h"
 #include "../../include/vcr_hip_refine.h"
 
 namespace {
@@ -219,10 +220,12 @@ __device__ __forceinline__ void rf_step_pose(const RfCloud& p, int b, double* Ri
 }
 
 // nn_plan on the search this call runs (under R_out / t_out), the arguments of its own checked first, and the workspace:
-// the scan's candidates | the partials | the per-cloud state
+// the scan's candidates | the partials | the per-cloud state | with the grid search (section 4.20), the grids
 struct RfPlan {
   NnPlan nn;
-  size_t part_off, pose_off, prev_off, live_off, iters_off, bytes;
+  size_t part_off, pose_off, prev_off, live_off, iters_off, grid_off, bytes;
+  bool on_grid;
+  GridNnPlan grid;
 };
 
 }  // namespace
@@ -230,8 +233,11 @@ struct RfPlan {
 // ------------------------------------------------------------------------------------------------------------------ the host
 
 // values: fp64 partials per 256 source points
-static int rf_plan(const vcr_refine_args& a, int cu, int values, RfPlan* p) {
+// ug: NULL = the scan.  Otherwise the grid search of include/vcr_hip_gridnn.h: the scan's variant must be 0, and the scan's plan
+// is taken at one target split -- the merge folds the grid search's one candidate a point
+static int rf_plan(const vcr_refine_args& a, const vcr_grid_nn_args* ug, int cu, int values, RfPlan* p) {
   *p = RfPlan{};
+  if (ug && a.variant != 0) return VCR_EINVAL;
   if (!a.R_out || !a.t_out || (a.R == nullptr) != (a.t == nullptr) || a.max_iterations < 0) return VCR_EINVAL;
   const float inf = __builtin_huge_valf();
   if (!(a.rel_fitness >= 0.f) || a.rel_fitness == inf || !(a.rel_rmse >= 0.f) || a.rel_rmse == inf) return VCR_EINVAL;
@@ -240,8 +246,8 @@ static int rf_plan(const vcr_refine_args& a, int cu, int values, RfPlan* p) {
   s.src = a.src; s.tgt = a.tgt; s.B = a.B; s.Ns = a.Ns; s.Nt = a.Nt;
   s.R = a.R_out; s.t = a.t_out; s.max_dist = a.max_dist;
   s.nn_idx = a.nn_idx; s.nn_d2 = a.nn_d2; s.inliers = a.inliers; s.sum_d2 = a.sum_d2; s.fitness = a.fitness; s.rmse = a.rmse;
-  s.variant = a.variant;
-  const int e = nn_plan(s, cu, &p->nn);
+  s.variant = ug ? VCR_NN_SCORE_VARIANT(1, 1) : a.variant;
+  int e = nn_plan(s, cu, &p->nn);
   if (e) return e;
   if (a.max_iterations > VCR_REFINE_MAX_ITERATIONS) return VCR_EUNSUPPORTED;
   const size_t B = (size_t)a.B;
@@ -250,7 +256,12 @@ static int rf_plan(const vcr_refine_args& a, int cu, int values, RfPlan* p) {
   p->prev_off = p->pose_off + ws_up(B * 12 * sizeof(double));
   p->live_off = p->prev_off + ws_up(B * 2 * sizeof(float));
   p->iters_off = p->live_off + ws_up(B * sizeof(int));
-  p->bytes = p->iters_off + ws_up(B * sizeof(int));
+  p->grid_off = p->bytes = p->iters_off + ws_up(B * sizeof(int));
+  if (ug) {
+    if ((e = gridnn_plan(ug, GRIDNN_REFINE, a.max_iterations + 1, a.B, a.Ns, a.Nt, &p->grid))) return e;
+    p->on_grid = true;
+    p->bytes += p->grid.bytes;
+  }
   return VCR_OK;
 }
 
@@ -262,11 +273,36 @@ static int rf_form(const typename Fit::Args* ua, int cu_count, int* queries_per_
   Fit fit;
   RfPlan p;
   if (Fit::take(ua, &a, &fit) || cu_count < 0) return VCR_EINVAL;
-  const int e = rf_plan(a, cu_count ? cu_count : vcr_cu_count(), Fit::VALUES, &p);
+  const int e = rf_plan(a, nullptr, cu_count ? cu_count : vcr_cu_count(), Fit::VALUES, &p);
   if (e) return e;
   if (queries_per_lane) *queries_per_lane = p.nn.Q;
   if (target_splits) *target_splits = p.nn.scan.S;
   return VCR_OK;
+}
+
+// The grid sibling's: no device is asked (neither plan depends on one)
+template <class Fit>
+static int rf_grid_form(const typename Fit::Args* ua, const vcr_grid_nn_args* ug, int cu_count, int* cells_per_cloud, int* order,
+                        int* queries_per_workgroup) {
+  vcr_refine_args a;
+  Fit fit;
+  RfPlan p;
+  if (Fit::take(ua, &a, &fit) || !ug || cu_count < 0) return VCR_EINVAL;
+  const int e = rf_plan(a, ug, 1, Fit::VALUES, &p);
+  if (e) return e;
+  if (cells_per_cloud) *cells_per_cloud = p.grid.cells;
+  if (order) *order = p.grid.order;
+  if (queries_per_workgroup) *queries_per_workgroup = VCR_GRID_QUERIES;
+  return VCR_OK;
+}
+
+template <class Fit>
+static size_t rf_grid_workspace_bytes(const typename Fit::Args* ua, const vcr_grid_nn_args* ug, int cu_count) {
+  vcr_refine_args a;
+  Fit fit;
+  RfPlan p;
+  if (Fit::take(ua, &a, &fit) || !ug || cu_count < 0) return 0;
+  return rf_plan(a, ug, 1, Fit::VALUES, &p) ? 0 : p.bytes;
 }
 
 template <class Fit>
@@ -275,23 +311,25 @@ static size_t rf_workspace_bytes(const typename Fit::Args* ua, int cu_count) {
   Fit fit;
   RfPlan p;
   if (Fit::take(ua, &a, &fit) || cu_count < 0) return 0;
-  return rf_plan(a, cu_count ? cu_count : vcr_cu_count(), Fit::VALUES, &p) ? 0 : p.bytes;
+  return rf_plan(a, nullptr, cu_count ? cu_count : vcr_cu_count(), Fit::VALUES, &p) ? 0 : p.bytes;
 }
 
-// One launch up front and three per round, max_iterations + 1 rounds, all enqueued at once (no host synchronisation)
+// One launch up front and three per round, max_iterations + 1 rounds, all enqueued at once (no host synchronisation).
+// search: the search that fills part_d2 / part_idx each round -- NULL = the scan (nn_scan_launch, in the form its plan says);
+// otherwise the grid search under these arguments (gridnn_search), its grids built once in front of round 0
 template <class Fit>
-static int rf_run(const typename Fit::Args* ua, void* workspace, size_t workspace_bytes, vcr_stream_t stream,
-                  void (*merge_kernel)(RfMerge<Fit>), void (*cloud_kernel)(RfCloud)) {
+static int rf_run(const typename Fit::Args* ua, const vcr_grid_nn_args* search, void* workspace, size_t workspace_bytes,
+                  vcr_stream_t stream, void (*merge_kernel)(RfMerge<Fit>), void (*cloud_kernel)(RfCloud)) {
   vcr_refine_args a;
   Fit fit;
   if (Fit::take(ua, &a, &fit)) return VCR_EINVAL;
-  // the argument checks need no device: only a call that passes them asks for the CU count
+  // the argument checks need no device: only a call that passes them asks for the CU count (the grid's plan needs none)
   RfPlan p;
-  int e = rf_plan(a, 1, Fit::VALUES, &p);
+  int e = rf_plan(a, search, 1, Fit::VALUES, &p);
   if (e) return e;
   if (!workspace || (((uintptr_t)workspace) & 15)) return VCR_EINVAL;
   vcr_stream_scope scope_(stream);
-  e = rf_plan(a, vcr_cu_count(), Fit::VALUES, &p);
+  if (!search) e = rf_plan(a, nullptr, vcr_cu_count(), Fit::VALUES, &p);
   if (e) return e;
   if (workspace_bytes < p.bytes) return VCR_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
@@ -303,10 +341,14 @@ static int rf_run(const typename Fit::Args* ua, void* workspace, size_t workspac
   const RfInit in{a.R, a.t, a.B, st, a.R_out, a.t_out, a.R_ba, a.t_ba};
   hipLaunchKernelGGL(refine_init_kernel, dim3((unsigned)((a.B + NN_BLOCK - 1) / NN_BLOCK)), dim3(NN_BLOCK), 0, s, in);
   if ((e = VCR_LAUNCH_RC())) return e;
+  if (p.on_grid && (e = gridnn_build(p.grid, a.src, a.tgt, w + p.grid_off, s))) return e;
   const RfMerge<Fit> mg{reinterpret_cast<const float*>(w), reinterpret_cast<const int*>(w + nn.part_bytes), a.src, a.tgt, a.R_out, a.t_out,
                         a.B, a.Ns, a.Nt, nn.scan.S, nn.nblk, a.max_dist * a.max_dist, a.nn_idx, a.nn_d2, part, st.live, fit};
   for (int round = 0; round <= a.max_iterations; ++round) {
-    if ((e = nn_scan_launch(nn, workspace, st.live, s))) return e;
+    e = p.on_grid ? gridnn_search(p.grid, a.src, a.R_out, a.t_out, a.max_dist * a.max_dist, w + p.grid_off,
+                                  reinterpret_cast<float*>(w), reinterpret_cast<int*>(w + nn.part_bytes), st.live, s)
+                  : nn_scan_launch(nn, workspace, st.live, s);
+    if (e) return e;
     hipLaunchKernelGGL(merge_kernel, dim3(nn.merge_grid), dim3(NN_BLOCK), 0, s, mg);
     if ((e = VCR_LAUNCH_RC())) return e;
     const RfCloud cl{part, a.Ns, nn.nblk, round, a.max_iterations, a.rel_fitness, a.rel_rmse, st,

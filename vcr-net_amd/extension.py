@@ -21,6 +21,14 @@ def workspace_signatures(entry, Args):
             entry + "_form": (_int, [C.POINTER(Args), _int, _intp, _intp])}
 
 
+def workspace_signatures2(entry, Args, Second):
+    """As workspace_signatures, for entry points that take a second struct behind the first (include/vcr_hip_gridnn.h); their
+    _form reports three ints."""
+    return {entry + "_workspace_bytes": (_size, [C.POINTER(Args), C.POINTER(Second), _int]),
+            entry + "_f32": (_int, [C.POINTER(Args), C.POINTER(Second), _vp, _size, _vp]),
+            entry + "_form": (_int, [C.POINTER(Args), C.POINTER(Second), _int, _intp, _intp, _intp])}
+
+
 def typed_lib(signatures):
     """-> lib(): native.lib() with `signatures` applied to it (once)."""
     typed = []
@@ -43,19 +51,20 @@ def form(L, entry, a, cu_count):
     return q.value, s.value, getattr(L, entry + "_workspace_bytes")(C.byref(a), cu_count)
 
 
-def call_with_workspace(L, entry, a, dev, prefill=None):
+def call_with_workspace(L, entry, a, dev, prefill=None, second=None):
     """`entry`_f32 on the args a with the workspace `entry`_workspace_bytes asks for, 256-aligned (filled with the byte
-    `prefill` first)."""
+    `prefill` first).  second: the struct an entry point of workspace_signatures2 takes behind a."""
     f32, workspace_bytes = getattr(L, entry + "_f32"), getattr(L, entry + "_workspace_bytes")
-    need = workspace_bytes(C.byref(a), 0)
+    structs = (C.byref(a),) if second is None else (C.byref(a), C.byref(second))
+    need = workspace_bytes(*structs, 0)
     if need == 0:                                            # refused: let the entry point say why
-        native.check(f32(C.byref(a), None, 0, native.stream_ptr()), entry + "_f32")
+        native.check(f32(*structs, None, 0, native.stream_ptr()), entry + "_f32")
         raise VcrHipError(f"{entry}_workspace_bytes: 0 for arguments {entry}_f32 accepts")
     ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
     if prefill is not None:
         ws.fill_(prefill)
     off = (-ws.data_ptr()) % 256
-    native.check(f32(C.byref(a), ws.data_ptr() + off, need, native.stream_ptr()), entry + "_f32")
+    native.check(f32(*structs, ws.data_ptr() + off, need, native.stream_ptr()), entry + "_f32")
 
 
 def outputs(dev, guard=0, prefill=None):

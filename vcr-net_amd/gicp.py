@@ -59,9 +59,14 @@ def _normals(src, tgt, src_normals, tgt_normals):
 
 
 def refine_gicp(src, tgt, src_normals, tgt_normals, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitness=1e-6,
-                rel_rmse=1e-6, variant=0, want_nn=True, guard=0, prefill=None, epsilon=EPSILON):
+                rel_rmse=1e-6, variant=0, want_nn=True, guard=0, prefill=None, epsilon=EPSILON, search="scan", cell=None, order=0):
     """vcr_refine_gicp_f32: refine.refine's arguments and dict, with src_normals [B,3,Ns] and tgt_normals [B,3,Nt] (device,
-    fp32, unit vectors of either sign) behind the clouds and epsilon, the covariance along a normal."""
+    fp32, unit vectors of either sign) behind the clouds and epsilon, the covariance along a normal.
+    search="grid": vcr_refine_gicp_grid_f32, as refine.refine's."""
+    from . import gridnn
+    gridnn.check_search("refine_registration", search)
+    gridnn.check_cell("refine_registration", cell)
     src_normals, tgt_normals = _normals(src, tgt, src_normals, tgt_normals)
     return refine.refine(src, tgt, R, t, max_dist, max_iterations, rel_fitness, rel_rmse, variant, want_nn, guard, prefill,
-                         tgt_normals=tgt_normals, src_normals=src_normals, epsilon=check_epsilon(epsilon))
+                         tgt_normals=tgt_normals, src_normals=src_normals, epsilon=check_epsilon(epsilon), search=search, cell=cell,
+                         order=order)

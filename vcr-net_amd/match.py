@@ -181,7 +181,7 @@ def ransac_correspondences(src, tgt, corr, max_dist, trials=100000, similarity=0
 
 def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials=100000, similarity=0.9, seed=0, refine=None,
                       refine_method="point_to_point", src_normals=None, tgt_normals=None, method="ransac", fgr=None,
-                      centre=False, search="knn"):
+                      centre=False, search="knn", nn_search="scan"):
     """Register two clouds of any two sizes with neither a network nor a starting pose: src [B,3,Ns], tgt [B,3,Nt] (float32
     device tensors).  compute_fpfh_feature(k, radius) on both, match_features(mutual), ransac_correspondences(max_dist,
     trials, similarity, seed), then score_registration at max_dist on the FULL clouds (Open3D's closing evaluation).
@@ -203,14 +203,18 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     RANSAC's own count.
     search: handed to both compute_fpfh_feature calls: "knn" is the brute-force search on the points' rows, "grid" takes the
     features' and the normals' neighbours from ``search_knn`` -- distances of differences, so the
-    features need no centring, and a point excluded from its own row by its index."""
-    from . import grid
+    features need no centring, and a point excluded from its own row by its index.  It means the feature stages' kNN and
+    nothing more.
+    ``nn_search``: the ``search`` of the score and refine steps: "scan" (the default) or "grid", the target's uniform grid
+     -- the same poses and scores bit for bit, faster on large clouds."""
+    from . import grid, gridnn
     grid.check_search("register_features", search)
+    gridnn.check_search("register_features", nn_search, "nn_search")
     if centre is not False and centre is not None:
         return _register_centred(src, tgt, max_dist, centre, refine,
                                  dict(k=k, radius=radius, mutual=mutual, trials=trials, similarity=similarity, seed=seed,
                                       refine=refine, refine_method=refine_method, src_normals=src_normals,
-                                      tgt_normals=tgt_normals, method=method, fgr=fgr, search=search))
+                                      tgt_normals=tgt_normals, method=method, fgr=fgr, search=search, nn_search=nn_search))
     from .fpfh import compute_fpfh_feature
     from .refine import refine_registration
     from .score import score_registration
@@ -220,21 +224,23 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     if method not in ("ransac", "fgr"):
         raise VcrHipError(f'{api}: method must be "ransac" or "fgr", got {method!r}')
     if method == "fgr":
-        return _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_method, src_normals, tgt_normals, fgr, search)
+        return _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_method, src_normals, tgt_normals, fgr, search,
+                             nn_search)
     if fgr is not None:
         raise VcrHipError(f'{api}: fgr= holds the keywords of method="fgr"; the method is "ransac"')
     _ransac_checks(api, src, tgt, None, max_dist, trials, similarity, seed, given_corr=False)
     corr = match_features(compute_fpfh_feature(src, src_normals, k=k, radius=radius, search=search),
                           compute_fpfh_feature(tgt, tgt_normals, k=k, radius=radius, search=search), mutual=mutual)
     r = ransac_correspondences(src, tgt, corr, max_dist, trials, similarity, seed)
-    res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist))
+    res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist, search=nn_search))
     res.update(R=r["R"], t=r["t"], best_trial=r["best_trial"], pairs=r["pairs"], ransac_inliers=r["inliers"], corr=corr)
     if refine is not None:
-        res["refined"] = refine_registration(src, tgt, r["R"], r["t"], float(refine), method=refine_method)
+        res["refined"] = refine_registration(src, tgt, r["R"], r["t"], float(refine), method=refine_method, search=nn_search)
     return res
 
 
-def _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_method, src_normals, tgt_normals, kw, search="knn"):
+def _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_method, src_normals, tgt_normals, kw, search="knn",
+                  nn_search="scan"):
     """register_features with method="fgr": the same chain with fast_global_registration in the RANSAC's place."""
     from . import fgr as F
     from .fpfh import compute_fpfh_feature
@@ -253,10 +259,10 @@ def _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_met
     corr = match_features(compute_fpfh_feature(src, src_normals, k=k, radius=radius, search=search),
                           compute_fpfh_feature(tgt, tgt_normals, k=k, radius=radius, search=search), mutual=mutual)
     r = F.fast_global_registration(src, tgt, corr, **kw)
-    res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist))
+    res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist, search=nn_search))
     res.update(R=r["R"], t=r["t"], pairs=r["pairs"], tuples=r["tuples"], used=r["used"], status=r["status"], corr=corr)
     if refine is not None:
-        res["refined"] = refine_registration(src, tgt, r["R"], r["t"], float(refine), method=refine_method)
+        res["refined"] = refine_registration(src, tgt, r["R"], r["t"], float(refine), method=refine_method, search=nn_search)
     return res
 
 
@@ -271,7 +277,7 @@ def _register_centred(src, tgt, max_dist, centre, refine, kw):
     src_c, c_src, tgt_c, c_tgt = take_centres(api, centre, src, tgt)
     res = register_features(src_c, tgt_c, max_dist, centre=False, **kw)
     _, res["t"] = uncentred_pose(res["R"], res["t"], c_src, c_tgt)
-    res.update(score_registration(src, tgt, res["R"], res["t"], float(max_dist)))
+    res.update(score_registration(src, tgt, res["R"], res["t"], float(max_dist), search=kw["nn_search"]))
     if "refined" in res:
-        res["refined"] = uncentre_refined(res["refined"], src, tgt, c_src, c_tgt, float(refine))
+        res["refined"] = uncentre_refined(res["refined"], src, tgt, c_src, c_tgt, float(refine), search=kw["nn_search"])
     return res

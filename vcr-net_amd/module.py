@@ -738,7 +738,7 @@ def vcrnetIter(net, src, tgt, iter=1):
 
 
 def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refine=None, refine_method="point_to_point",
-                     voxel=None, outlier=None):
+                     voxel=None, nn_search="scan", outlier=None):
     """Register two clouds of ANY size: src [B,3,Ns] and tgt [B,3,Nt] (Ns != Nt allowed, each up to 131 072 points) are reduced
     to ``npoint`` points each by farthest-point sampling on the device (two vcr_fps_f32 launches, the reference's
     farthest_point_sample index for index), and ``vcrnetIter(net, src_s, tgt_s, iter)`` runs on the sampled clouds.  The
@@ -763,7 +763,11 @@ def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refi
     the raw clouds otherwise.  The filter too leaves every cloud its own size, so the call takes ``voxel``'s cloud-by-cloud
     route and returns in its form: the filter's counts travel to the host in the same ONE synchronisation as the voxel
     counts, the indices and the last element refer to the FILTERED clouds, and a cloud left with fewer than ``npoint`` points
-    raises."""
+    raises.
+    ``nn_search``: the ``search`` of the score and refine steps: "scan" (the default) or "grid", the target's uniform grid
+     -- the same poses and scores bit for bit, faster on large clouds."""
+    from . import gridnn
+    gridnn.check_search("register_sampled", nn_search, "nn_search")
     for name, x in (("src", src), ("tgt", tgt)):
         if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != 3:
             raise native.VcrHipError(f"register_sampled: {name} must be a [B, 3, N] point cloud, got "
@@ -776,20 +780,22 @@ def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refi
                                  "(there is no CPU fallback by design)")
     s_src, s_tgt = (None, None) if start is None else start
     if voxel is not None or outlier is not None:
-        return _register_voxelised(net, src, tgt, npoint, iter, s_src, s_tgt, score, refine, refine_method, voxel, outlier)
+        return _register_voxelised(net, src, tgt, npoint, iter, s_src, s_tgt, score, refine, refine_method, voxel, outlier,
+                                   nn_search)
     idx_s, src_s = native.fps(src.float(), npoint, start=s_src)
     idx_t, tgt_s = native.fps(tgt.float(), npoint, start=s_tgt)
     out = tuple(vcrnetIter(net, src_s, tgt_s, iter)) + (idx_s.long(), idx_t.long())
     if score is not None:
         from .score import score_registration
-        out += (score_registration(src, tgt, out[2], out[3], max_dist=score),)
+        out += (score_registration(src, tgt, out[2], out[3], max_dist=score, search=nn_search),)
     if refine is not None:
         from .refine import refine_registration
-        out += (refine_registration(src, tgt, out[2], out[3], max_dist=refine, method=refine_method),)
+        out += (refine_registration(src, tgt, out[2], out[3], max_dist=refine, method=refine_method, search=nn_search),)
     return out
 
 
-def _register_voxelised(net, src, tgt, npoint, iter, s_src, s_tgt, score, refine, refine_method, voxel, outlier=None):
+def _register_voxelised(net, src, tgt, npoint, iter, s_src, s_tgt, score, refine, refine_method, voxel, outlier=None,
+                        nn_search="scan"):
     """register_sampled(voxel=h, outlier=spec): the clouds down-sampled on the grid and / or filtered, then the same steps
     cloud by cloud."""
     from . import voxel as vx
@@ -827,8 +833,9 @@ def _register_voxelised(net, src, tgt, npoint, iter, s_src, s_tgt, score, refine
     pairs = [(src_d[b].unsqueeze(0), tgt_d[b].unsqueeze(0), out[2][b:b + 1], out[3][b:b + 1]) for b in range(B)]
     if score is not None:
         from .score import score_registration
-        out += ([score_registration(s, t, R, tr, max_dist=score) for s, t, R, tr in pairs],)
+        out += ([score_registration(s, t, R, tr, max_dist=score, search=nn_search) for s, t, R, tr in pairs],)
     if refine is not None:
         from .refine import refine_registration
-        out += ([refine_registration(s, t, R, tr, max_dist=refine, method=refine_method) for s, t, R, tr in pairs],)
+        out += ([refine_registration(s, t, R, tr, max_dist=refine, method=refine_method, search=nn_search)
+                 for s, t, R, tr in pairs],)
     return out + ((src_d, tgt_d),)

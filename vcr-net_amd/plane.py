@@ -105,8 +105,12 @@ def estimate_normals(xyz, k=20, viewpoint=None, want_curvature=False, want_idx=F
 
 
 def refine_plane(src, tgt, tgt_normals, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6,
-                 variant=0, want_nn=True, guard=0, prefill=None):
-    """vcr_refine_plane_f32: refine.refine's arguments and dict, with tgt_normals [B,3,Nt] (device, fp32) behind tgt."""
+                 variant=0, want_nn=True, guard=0, prefill=None, search="scan", cell=None, order=0):
+    """vcr_refine_plane_f32: refine.refine's arguments and dict, with tgt_normals [B,3,Nt] (device, fp32) behind tgt.
+    search="grid": vcr_refine_plane_grid_f32, as refine.refine's."""
+    from . import gridnn
+    gridnn.check_search("refine_registration", search)
+    gridnn.check_cell("refine_registration", cell)
     refine._cloud("tgt", tgt)
     if not torch.is_tensor(tgt_normals) or tuple(tgt_normals.shape) != tuple(tgt.shape):
         raise VcrHipError(f"refine_registration: tgt_normals must be [B, 3, Nt] like tgt {tuple(tgt.shape)}, got "
@@ -114,4 +118,4 @@ def refine_plane(src, tgt, tgt_normals, R=None, t=None, max_dist=0.0, max_iterat
     if not tgt_normals.is_cuda or tgt_normals.device != tgt.device:
         raise VcrHipError("refine_registration: tgt_normals must live on the device of the clouds (there is no CPU fallback)")
     return refine.refine(src, tgt, R, t, max_dist, max_iterations, rel_fitness, rel_rmse, variant, want_nn, guard, prefill,
-                         tgt_normals=tgt_normals.contiguous().float())
+                         tgt_normals=tgt_normals.contiguous().float(), search=search, cell=cell, order=order)

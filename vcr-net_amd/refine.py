@@ -54,7 +54,7 @@ def _threshold(name, v):
 
 @native._guarded
 def refine(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6, variant=0, want_nn=True,
-           guard=0, prefill=None, tgt_normals=None, src_normals=None, epsilon=None):
+           guard=0, prefill=None, tgt_normals=None, src_normals=None, epsilon=None, search="scan", cell=None, order=0):
     """vcr_refine_f32 on src [B,3,Ns], tgt [B,3,Nt] (device, fp32) from the pose (R [B,3,3], t [B,3]; both None = identity)
     -> dict of R [B,3,3], t [B,3], R_ba, t_ba, fitness, rmse float32 [B], inliers, iterations, converged int32 [B], sum_d2
     float64 [B], nn_idx int32 / nn_d2 [B,Ns] (want_nn).
@@ -62,7 +62,12 @@ def refine(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitnes
     workspace -- filled with the byte `prefill` before the launch; the buffers come back under "_raw".
     tgt_normals [B,3,Nt]: vcr_refine_plane_f32 instead -- the same loop with the point-to-plane fit (plane.refine_plane checks
     them and calls this).  With src_normals [B,3,Ns] and epsilon as well: vcr_refine_gicp_f32, the plane-to-plane fit
-    (gicp.refine_gicp checks them and calls this)."""
+    (gicp.refine_gicp checks them and calls this).
+    search="grid": the entry point's grid sibling instead (include/vcr_hip_gridnn.h; variant must be 0), with cell (None: the
+    automatic edge) and order (0 = the plan's, 1 = the source's cell order, 2 = index order) as its vcr_grid_nn_args."""
+    from . import gridnn
+    gridnn.check_search("refine_registration", search)
+    cell = gridnn.check_cell("refine_registration", cell)
     extension.check_pair("refine_registration", src, tgt, R, t)
     max_dist = _threshold("max_dist", max_dist)
     rel_fitness, rel_rmse = _threshold("rel_fitness", rel_fitness), _threshold("rel_rmse", rel_rmse)
@@ -93,7 +98,10 @@ def refine(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitnes
         a.tgt_normals = ptr(tgt_normals)
     if src_normals is not None:
         a.src_normals, a.epsilon = ptr(src_normals), epsilon
-    extension.call_with_workspace(L, entry, a, dev, prefill)
+    if search == "grid":
+        extension.call_with_workspace(gridnn.lib(), gridnn.entry_of(entry), a, dev, prefill, second=gridnn.grid_args(cell, order))
+    else:
+        extension.call_with_workspace(L, entry, a, dev, prefill)
     if guard or prefill is not None:
         o["_raw"] = raw
     return o
@@ -104,7 +112,7 @@ METHODS = ("point_to_point", "point_to_plane", "generalized")
 
 def refine_registration(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6,
                         want_nn=False, method="point_to_point", tgt_normals=None, normal_k=20, src_normals=None, epsilon=1e-3,
-                        centre=False):
+                        centre=False, search="scan", cell=None):
     """Improve the pose (R, t) on the FULL clouds: src [B,3,Ns], tgt [B,3,Nt] (Ns != Nt allowed, each up to 131 072 points;
     device tensors).  An ICP: every round matches each moved source point to its nearest target point, keeps the pairs within
     max_dist and solves the best rigid update for them; a cloud stops on its own when fitness and inlier RMSE both change by
@@ -129,7 +137,20 @@ def refine_registration(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=3
     the target each to its own centre first (``centred``: the mean of the finite coordinates), a pair (c_src, c_tgt) of [B,3]
     tensors to the centres given -- before anything else, the normals estimated inside included --, runs the method there,
     carries R, t, R_ba, t_ba back (``uncentred_pose``) and takes fitness, inlier_rmse, inliers, nn_idx and nn_d2 from the
-    caller's clouds at the returned pose."""
+    caller's clouds at the returned pose.
+    search: "scan" (the default) tests every source point against every target point.  "grid" walks the target's uniform grid
+     and stops at max_dist: the same inliers, fitness, inlier_rmse, poses, iterations and converged,
+    bit for bit; the one difference is that a source point without a target point within max_dist reports nn_idx = -1,
+    nn_d2 = +inf where the scan reports the far neighbour it found.  Measured (DESIGN.md section 4.20,
+    profiles/gridnn_bench.txt): it wins from about 16 384 points for one cloud and 4 096 points a cloud for sixteen (x5-x10 an
+    evaluation, x12-x25 a round at 131 072 points) and loses below; it loses on clouds that fill little of their bounding box
+    (tight clusters); with many source points without a partner inside the target's box its advantage falls from x7-x9.5 at
+    max_dist <= 1 automatic grid edge to x3-x5 at 4 edges and x1.2-x1.7 at 8: take it for max_dist up to about four edges.
+    cell: None for the target's automatic edge, otherwise the cells' edge -- it changes the time and never the result.
+    It serves every round of the three methods and the closing evaluation of centre."""
+    from . import gridnn
+    gridnn.check_search("refine_registration", search)
+    gridnn.check_cell("refine_registration", cell)
     if method not in METHODS:
         raise VcrHipError(f"refine_registration: method must be one of {METHODS}, got {method!r}")
     if method != "generalized" and (src_normals is not None or epsilon != 1e-3):
@@ -138,7 +159,8 @@ def refine_registration(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=3
         extension.check_pair("refine_registration", src, tgt, R, t)
         return _refine_centred(src, tgt, R, t, max_dist, centre, want_nn,
                                dict(max_iterations=max_iterations, rel_fitness=rel_fitness, rel_rmse=rel_rmse, method=method,
-                                    tgt_normals=tgt_normals, normal_k=normal_k, src_normals=src_normals, epsilon=epsilon))
+                                    tgt_normals=tgt_normals, normal_k=normal_k, src_normals=src_normals, epsilon=epsilon,
+                                    search=search, cell=cell))
     if method == "generalized":
         from . import gicp, plane
         _cloud("src", src)
@@ -149,18 +171,19 @@ def refine_registration(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=3
         if src_normals is None:
             src_normals = plane.estimate_normals(src, normal_k)
         f = gicp.refine_gicp(src, tgt, src_normals, tgt_normals, R, t, max_dist, max_iterations, rel_fitness, rel_rmse,
-                             want_nn=want_nn, epsilon=epsilon)
+                             want_nn=want_nn, epsilon=epsilon, search=search, cell=cell)
     elif method == "point_to_plane":
         from . import plane
         _cloud("src", src)
         _cloud("tgt", tgt)
         if tgt_normals is None:
             tgt_normals = plane.estimate_normals(tgt, normal_k)
-        f = plane.refine_plane(src, tgt, tgt_normals, R, t, max_dist, max_iterations, rel_fitness, rel_rmse, want_nn=want_nn)
+        f = plane.refine_plane(src, tgt, tgt_normals, R, t, max_dist, max_iterations, rel_fitness, rel_rmse, want_nn=want_nn,
+                               search=search, cell=cell)
     else:
         if tgt_normals is not None:
             raise VcrHipError("refine_registration: tgt_normals are read by method='point_to_plane' only")
-        f = refine(src, tgt, R, t, max_dist, max_iterations, rel_fitness, rel_rmse, want_nn=want_nn)
+        f = refine(src, tgt, R, t, max_dist, max_iterations, rel_fitness, rel_rmse, want_nn=want_nn, search=search, cell=cell)
     res = {"R": f["R"], "t": f["t"], "R_ba": f["R_ba"], "t_ba": f["t_ba"], "fitness": f["fitness"], "inlier_rmse": f["rmse"],
            "inliers": f["inliers"], "iterations": f["iterations"], "converged": f["converged"]}
     if want_nn:
@@ -168,7 +191,7 @@ def refine_registration(src, tgt, R=None, t=None, max_dist=0.0, max_iterations=3
     return res
 
 
-def uncentre_refined(res, src, tgt, c_src, c_tgt, max_dist, want_nn=False):
+def uncentre_refined(res, src, tgt, c_src, c_tgt, max_dist, want_nn=False, search="scan", cell=None):
     """refine_registration's dict from clouds centred at c_src, c_tgt -> the same in the caller's frame: the poses carried back,
     the evaluation taken again on the caller's clouds (src, tgt) at the pose returned."""
     from .centre import uncentred_pose
@@ -176,7 +199,7 @@ def uncentre_refined(res, src, tgt, c_src, c_tgt, max_dist, want_nn=False):
     out = dict(res)
     _, out["t"] = uncentred_pose(res["R"], res["t"], c_src, c_tgt)
     _, out["t_ba"] = uncentred_pose(res["R_ba"], res["t_ba"], c_tgt, c_src)
-    out.update(score_registration(src, tgt, out["R"], out["t"], max_dist, want_nn=want_nn))
+    out.update(score_registration(src, tgt, out["R"], out["t"], max_dist, want_nn=want_nn, search=search, cell=cell))
     return out
 
 
@@ -191,4 +214,4 @@ def _refine_centred(src, tgt, R, t, max_dist, centre, want_nn, kw):
         R, t = R.contiguous().float(), t.contiguous().float()
     R_c, t_c = centred_pose(R, t, c_src, c_tgt)
     res = refine_registration(src_c, tgt_c, R_c, t_c, max_dist, want_nn=False, centre=False, **kw)
-    return uncentre_refined(res, src, tgt, c_src, c_tgt, max_dist, want_nn)
+    return uncentre_refined(res, src, tgt, c_src, c_tgt, max_dist, want_nn, search=kw["search"], cell=kw["cell"])

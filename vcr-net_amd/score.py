@@ -48,11 +48,18 @@ def nn_score_form(B, Ns, Nt, cu_count=256, variant=0):
 
 
 @native._guarded
-def nn_score(src, tgt, R=None, t=None, max_dist=0.0, variant=0, want_nn=True, guard=0, prefill=None):
+def nn_score(src, tgt, R=None, t=None, max_dist=0.0, variant=0, want_nn=True, guard=0, prefill=None, search="scan", cell=None,
+             order=0):
     """vcr_nn_score_f32 on src [B,3,Ns], tgt [B,3,Nt] (device, fp32) under the pose (R [B,3,3], t [B,3]; both None = identity)
     -> dict of nn_idx int32 [B,Ns], nn_d2 [B,Ns] (want_nn), inliers int32 [B], sum_d2 float64 [B], fitness, rmse float32 [B].
     guard / prefill (tests): every output is a view of a buffer with `guard` more elements behind it, all of it filled with the
-    byte `prefill` before the launch; the buffers come back under "_raw"."""
+    byte `prefill` before the launch; the buffers come back under "_raw".
+    search="grid": vcr_nn_score_grid_f32 instead (include/vcr_hip_gridnn.h; variant must be 0), with cell (None: the automatic
+    edge) and order (0 = the plan's, 1 = the source's cell order, 2 = index order) as its vcr_grid_nn_args; the workspace is
+    prefilled too."""
+    from . import gridnn
+    gridnn.check_search("score_registration", search)
+    cell = gridnn.check_cell("score_registration", cell)
     extension.check_pair("score_registration", src, tgt, R, t)
     max_dist = float(max_dist)
     if not (math.isfinite(max_dist) and max_dist >= 0.0):
@@ -66,13 +73,16 @@ def nn_score(src, tgt, R=None, t=None, max_dist=0.0, variant=0, want_nn=True, gu
     o["fitness"], o["rmse"] = out("fitness", B, torch.float32), out("rmse", B, torch.float32)
     a = NnScoreArgs(ptr(src), ptr(tgt), B, Ns, Nt, ptr(R), ptr(t), max_dist, ptr(o.get("nn_idx")), ptr(o.get("nn_d2")),
                     ptr(o["inliers"]), ptr(o["sum_d2"]), ptr(o["fitness"]), ptr(o["rmse"]), int(variant))
-    extension.call_with_workspace(lib(), "vcr_nn_score", a, dev)
+    if search == "grid":
+        extension.call_with_workspace(gridnn.lib(), "vcr_nn_score_grid", a, dev, prefill, second=gridnn.grid_args(cell, order))
+    else:
+        extension.call_with_workspace(lib(), "vcr_nn_score", a, dev)
     if guard or prefill is not None:
         o["_raw"] = raw
     return o
 
 
-def score_registration(src, tgt, R=None, t=None, max_dist=0.0, symmetric=False, want_nn=False):
+def score_registration(src, tgt, R=None, t=None, max_dist=0.0, symmetric=False, want_nn=False, search="scan", cell=None):
     """How good is the pose (R, t) for the FULL clouds?  src [B,3,Ns], tgt [B,3,Nt] (Ns != Nt allowed, each up to 131 072
     points; device tensors): every source point is moved by the pose and matched to its nearest target point.  Returns a dict:
       fitness      float32 [B]   the fraction of source points within max_dist of the target
@@ -81,8 +91,18 @@ def score_registration(src, tgt, R=None, t=None, max_dist=0.0, symmetric=False, 
       nn_idx, nn_d2 (want_nn)    int64 / float32 [B,Ns]: the neighbour (the lowest index among equals; -1 when no target point
                                  is at a finite distance) and the squared distance to it
     symmetric: also tgt -> src under the inverse pose (native.pose_step's R_ba, t_ba), as fitness_ba, inlier_rmse_ba,
-    inliers_ba.  R = t = None: the identity."""
-    f = nn_score(src, tgt, R, t, max_dist, want_nn=want_nn)
+    inliers_ba.  R = t = None: the identity.
+    search: "scan" (the default) tests every source point against every target point.  "grid" walks the target's uniform grid
+     and stops at max_dist: the same inliers, fitness, inlier_rmse and poses, bit for bit; the one
+    difference is that a source point without a target point within max_dist reports nn_idx = -1, nn_d2 = +inf where the scan
+    reports the far neighbour it found.  Measured (DESIGN.md section 4.20,
+    profiles/gridnn_bench.txt): it wins from about 16 384 points for one cloud and 4 096 points a cloud for sixteen (x5-x10 an
+    evaluation, x12-x25 a round at 131 072 points) and loses below; it loses on clouds that fill little of their bounding box
+    (tight clusters); with many source points without a partner inside the target's box its advantage falls from x7-x9.5 at
+    max_dist <= 1 automatic grid edge to x3-x5 at 4 edges and x1.2-x1.7 at 8: take it for max_dist up to about four edges.
+    cell: None for the target's automatic edge, otherwise the cells' edge -- it changes the time and never the result.
+    With symmetric, the way back is searched the same way (on the source's grid; a forced cell serves both)."""
+    f = nn_score(src, tgt, R, t, max_dist, want_nn=want_nn, search=search, cell=cell)
     res = {"fitness": f["fitness"], "inlier_rmse": f["rmse"], "inliers": f["inliers"]}
     if want_nn:
         res["nn_idx"], res["nn_d2"] = f["nn_idx"].long(), f["nn_d2"]
@@ -90,6 +110,6 @@ def score_registration(src, tgt, R=None, t=None, max_dist=0.0, symmetric=False, 
         R_ba = t_ba = None
         if R is not None:
             _, _, _, R_ba, t_ba = native.pose_step(R, t)
-        g = nn_score(tgt, src, R_ba, t_ba, max_dist, want_nn=False)
+        g = nn_score(tgt, src, R_ba, t_ba, max_dist, want_nn=False, search=search, cell=cell)
         res.update(fitness_ba=g["fitness"], inlier_rmse_ba=g["rmse"], inliers_ba=g["inliers"])
     return res
