@@ -738,7 +738,7 @@ def vcrnetIter(net, src, tgt, iter=1):
 
 
 def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refine=None, refine_method="point_to_point",
-                     voxel=None, nn_search="scan", outlier=None):
+                     voxel=None, nn_search="scan", voxel_method="scan", outlier=None):
     """Register two clouds of ANY size: src [B,3,Ns] and tgt [B,3,Nt] (Ns != Nt allowed, each up to 131 072 points) are reduced
     to ``npoint`` points each by farthest-point sampling on the device (two vcr_fps_f32 launches, the reference's
     farthest_point_sample index for index), and ``vcrnetIter(net, src_s, tgt_s, iter)`` runs on the sampled clouds.  The
@@ -765,9 +765,13 @@ def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refi
     counts, the indices and the last element refer to the FILTERED clouds, and a cloud left with fewer than ``npoint`` points
     raises.
     ``nn_search``: the ``search`` of the score and refine steps: "scan" (the default) or "grid", the target's uniform grid
-     -- the same poses and scores bit for bit, faster on large clouds."""
+     -- the same poses and scores bit for bit, faster on large clouds.
+    ``voxel_method``: the ``method`` of ``voxel``'s ``voxel_down_sample``: "scan" (the default) or "sort" (DESIGN.md section
+    4.21) -- the same clouds bit for bit, faster on large ones."""
     from . import gridnn
     gridnn.check_search("register_sampled", nn_search, "nn_search")
+    if voxel_method not in ("scan", "sort"):
+        raise native.VcrHipError(f'register_sampled: voxel_method must be "scan" or "sort", got {voxel_method!r}')
     for name, x in (("src", src), ("tgt", tgt)):
         if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != 3:
             raise native.VcrHipError(f"register_sampled: {name} must be a [B, 3, N] point cloud, got "
@@ -781,7 +785,7 @@ def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refi
     s_src, s_tgt = (None, None) if start is None else start
     if voxel is not None or outlier is not None:
         return _register_voxelised(net, src, tgt, npoint, iter, s_src, s_tgt, score, refine, refine_method, voxel, outlier,
-                                   nn_search)
+                                   nn_search, voxel_method)
     idx_s, src_s = native.fps(src.float(), npoint, start=s_src)
     idx_t, tgt_s = native.fps(tgt.float(), npoint, start=s_tgt)
     out = tuple(vcrnetIter(net, src_s, tgt_s, iter)) + (idx_s.long(), idx_t.long())
@@ -795,15 +799,15 @@ def register_sampled(net, src, tgt, npoint, iter=1, start=None, score=None, refi
 
 
 def _register_voxelised(net, src, tgt, npoint, iter, s_src, s_tgt, score, refine, refine_method, voxel, outlier=None,
-                        nn_search="scan"):
+                        nn_search="scan", voxel_method="scan"):
     """register_sampled(voxel=h, outlier=spec): the clouds down-sampled on the grid and / or filtered, then the same steps
     cloud by cloud."""
     from . import voxel as vx
     B = src.shape[0]
     ps, pt, counts = src, tgt, []
     if voxel is not None:
-        ps, cs, _ = vx.voxel_down_sample(src, voxel)
-        pt, ct, _ = vx.voxel_down_sample(tgt, voxel)
+        ps, cs, _ = vx.voxel_down_sample(src, voxel, method=voxel_method)
+        pt, ct, _ = vx.voxel_down_sample(tgt, voxel, method=voxel_method)
         counts += [cs, ct]
     if outlier is not None:
         # on the padded batches: the NaN points behind a cloud's voxels are dropped and seen by nobody (a cloud's result is a

@@ -74,15 +74,26 @@ def voxel_grid(xyz, voxel_size, variant=0, want_trace=True, guard=0, prefill=Non
     return o
 
 
-def voxel_down_sample(xyz, voxel_size):
+def voxel_down_sample(xyz, voxel_size, method="scan"):
     """xyz [B,3,N] (device tensor, up to 131 072 points a cloud) on a grid of edge voxel_size: every occupied cell gives one
     point, the mean of the points inside it (Open3D's voxel_down_sample; its grid starts at the finite points' minimum minus
     voxel_size / 2).  Returns (points, count, point_voxel) without a host synchronisation:
       points       float32 [B,3,N]  cloud b's count[b] voxels in order of first appearance, NaN behind them
       count        int32 [B]        -1 where the grid is too fine for the cloud (more than 2^21 cells along an axis)
       point_voxel  int32 [B,N]      the voxel every point went to, -1 for a point with a NaN or infinite coordinate
-    ``unpad(points, count)`` cuts the clouds to their sizes."""
-    o = voxel_grid(xyz, voxel_size, want_trace=True)
+    ``unpad(points, count)`` cuts the clouds to their sizes.
+    ``method``: "scan" (the default: every point against every point, vcr_voxel_f32) or "sort" (a stable device radix sort of
+    the points' cells, vcr_voxel_sort_f32) -- the same bits either way; anything else raises.
+    Measured (profiles/voxel_sort_bench.txt, ~8 points a voxel): "sort" is worth taking from about 4 096 points a cloud (x1.5 for
+    one cloud, x1.9 for sixteen; x39 at 131 072 points), is a draw at 2 048 and loses at 1 024 (x0.78), where its fixed 28
+    launches cost more than the scan."""
+    if method == "sort":
+        from . import voxel_sort
+        o = voxel_sort.voxel_grid_sort(xyz, voxel_size, want_trace=True)
+    elif method == "scan":
+        o = voxel_grid(xyz, voxel_size, want_trace=True)
+    else:
+        raise VcrHipError(f'voxel_down_sample: method must be "scan" or "sort", got {method!r}')
     return o["points"], o["count"], o["point_voxel"]
 
 
