@@ -14,7 +14,7 @@ from . import weights, synth  # noqa: F401
 __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "score_registration", "refine_registration",
            "estimate_normals", "voxel_down_sample", "remove_statistical_outlier", "remove_radius_outlier", "compute_fpfh_feature",
            "match_features", "ransac_correspondences", "register_features", "fast_global_registration", "centred",
-           "uncentred_pose", "search_knn"]
+           "uncentred_pose", "search_knn", "search_radius"]
 
 
 def __getattr__(name):
@@ -52,6 +52,9 @@ def __getattr__(name):
     if name == "search_knn":
         from .grid import search_knn
         return search_knn
+    if name == "search_radius":
+        from .radius import search_radius
+        return search_radius
     if name in ("centred", "uncentred_pose"):
         from . import centre
         return getattr(centre, name)

@@ -53,6 +53,33 @@ __device__ __forceinline__ int wg_offsets(int* cnt, int nblk, int* wtot) {
   return carry;
 }
 
+// wg_offsets' sibling for sums that may pass 2^31: out [n] (int64) becomes the exclusive scan of cnt [n] (int32, >= 0), not in
+// place (the same two counts a lane, wave scan and four wave totals, in 64-bit); every lane returns the total.  wtot [WG_WAVES].
+__device__ __forceinline__ long long wg_offsets64(const int* cnt, long long* out, int n, long long* wtot) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  long long carry = 0;
+  for (int c0 = 0; c0 < n; c0 += 2 * WG_BLOCK) {           // (workgroup-uniform: 256 rounds at 131 072 counts)
+    const int i0 = c0 + 2 * t, i1 = i0 + 1;
+    const long long a0 = i0 < n ? cnt[i0] : 0, a1 = i1 < n ? cnt[i1] : 0;
+    long long incl = a0 + a1;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const long long v = __shfl_up(incl, o, 64);
+      incl += lane >= o ? v : 0;
+    }
+    __syncthreads();                                       // the previous round's totals have been read
+    if (lane == 63) wtot[w] = incl;
+    __syncthreads();
+    long long below = 0, all = 0;
+    for (int k = 0; k < WG_WAVES; ++k) { below += k < w ? wtot[k] : 0; all += wtot[k]; }
+    const long long excl = carry + below + incl - (a0 + a1);
+    if (i0 < n) out[i0] = excl;
+    if (i1 < n) out[i1] = excl + a0;
+    carry += all;
+  }
+  return carry;
+}
+
 // The workgroup's 256 (v, c): the wave butterfly 32 ... 1, then the four waves ascending.  Thread 0 alone returns the sums;
 // wsum / wcnt [WG_WAVES] are free again after the caller's next barrier.
 __device__ __forceinline__ void wg_sum_count(double v, int c, int t, double* wsum, int* wcnt, double* sum, int* cnt) {

@@ -1,6 +1,6 @@
 """ctypes binding of include/vcr_hip_outlier.h and the Python API on top of it: removing a cloud's stray
 points on the device -- Open3D's remove_statistical_outlier (vcr_outlier_stat_f32, on the library's kNN) and
-remove_radius_outlier (vcr_outlier_radius_f32, a brute-force count) -- the step between ``voxel_down_sample`` and
+remove_radius_outlier (vcr_outlier_radius_f32, a brute-force count, or its grid sibling of ``radius``) -- the step between ``voxel_down_sample`` and
 ``estimate_normals``.
 
 The header extends include/vcr_hip.h without touching it, and so does this module for ``native``: its own STRUCTS / SIGNATURES
@@ -169,20 +169,32 @@ def remove_statistical_outlier(xyz, nb_neighbors=20, std_ratio=2.0, search="knn"
     return o["points"], o["count"], o["index"]
 
 
-def remove_radius_outlier(xyz, nb_points, radius):
+def remove_radius_outlier(xyz, nb_points, radius, search="scan"):
     """xyz [B,3,N] (device tensor, up to 131 072 points a cloud) without the points that have no more than nb_points points
     (themselves included, as Open3D counts) within radius: Open3D's remove_radius_outlier.  The distances are differences
     (dx^2 + dy^2 + dz^2 in fp32, a point ON the sphere counts), so a cloud far from the origin needs no centring.  Returns
     (points, count, index) as remove_statistical_outlier, without a host synchronisation; ``voxel.unpad(points, count)`` cuts
-    the clouds to their sizes.  A point with a NaN or infinite coordinate is dropped and counted by nobody."""
-    o = radius_filter(xyz, radius, nb_points, want_trace=False)
+    the clouds to their sizes.  A point with a NaN or infinite coordinate is dropped and counted by nobody.
+    search: "scan" compares every point with every point.  "grid" counts on the cloud's uniform grid instead (DESIGN.md section
+    4.22: cells of the radius' edge, 27 of them a point where the cloud is no denser than its grid) and returns the same bits;
+    it needs a radius whose fp32 square is finite."""
+    if search not in ("scan", "grid"):
+        raise VcrHipError(f'remove_radius_outlier: search must be "scan" or "grid", got {search!r}')
+    if search == "grid":
+        from . import radius as radius_search               # (it imports this module: resolved on first use)
+        o = radius_search.radius_filter_grid(xyz, radius, nb_points, want_trace=False)
+    else:
+        o = radius_filter(xyz, radius, nb_points, want_trace=False)
     return o["points"], o["count"], o["index"]
 
 
 def filter_by(spec, xyz):
     """register_sampled's ``outlier=`` on one batch: ("statistical", nb_neighbors, std_ratio) or ("radius", nb_points, radius)
-    -> (points, count, index)."""
-    if not (isinstance(spec, (tuple, list)) and len(spec) == 3 and spec[0] in ("statistical", "radius")):
+    -> (points, count, index).  The radius filter takes an optional fourth element, "grid": its ``search=``."""
+    ok = isinstance(spec, (tuple, list)) and len(spec) >= 1 and spec[0] in ("statistical", "radius")
+    if not (ok and (len(spec) == 3 or (spec[0] == "radius" and len(spec) == 4 and spec[3] == "grid"))):
         raise VcrHipError('register_sampled: outlier must be ("statistical", nb_neighbors, std_ratio) or '
                           f'("radius", nb_points, radius), got {spec!r}')
-    return remove_statistical_outlier(xyz, spec[1], spec[2]) if spec[0] == "statistical" else remove_radius_outlier(xyz, spec[1], spec[2])
+    if spec[0] == "statistical":
+        return remove_statistical_outlier(xyz, spec[1], spec[2])
+    return remove_radius_outlier(xyz, spec[1], spec[2], *spec[3:])
