@@ -10,7 +10,7 @@ import ctypes as C
 import math
 import torch
 
-from . import extension, grid, native, plane
+from . import extension, grid, native, plane, rows
 from .native import VcrHipError, f32p, ptr
 from .score import i32p
 
@@ -82,7 +82,8 @@ def fpfh(xyz4, idx, spfh, radius=0.0, guard=0, prefill=None):
     return (feat, raw) if guard or prefill is not None else feat
 
 
-def compute_fpfh_feature(xyz, normals=None, k=30, radius=None, want_normals=False, want_idx=False, search="knn"):
+def compute_fpfh_feature(xyz, normals=None, k=30, radius=None, want_normals=False, want_idx=False, search="knn", max_nn=None,
+                         capacity=None):
     """The 33-bin Fast Point Feature Histogram of every point of xyz [B,3,N] (device tensor, up to 131 072 points a cloud) from
     its k nearest neighbours: Open3D's compute_fpfh_feature, in fp64 on the device.  Returns float32 [B,33,N] -- three groups
     of 11 bins, each group of a point summing to 200 where the point and a neighbour have pairs to count; with want_normals
@@ -96,9 +97,16 @@ def compute_fpfh_feature(xyz, normals=None, k=30, radius=None, want_normals=Fals
     ``vcrnet_amd.centred(xyz)`` returns xyz - c and the centre c it took.
     search: "knn" is that search.  "grid" takes the neighbours (the normals' too) from ``search_knn``
     instead: distances of differences, so no centring is needed, and the point itself excluded by its index.  The faster one
-    for large clouds."""
+    for large clouds.
+    search="radius" (DESIGN.md section 4.23): the neighbourhood is ALL points within `radius` (``search_radius``, rows of any
+    length: Open3D's KDTreeSearchParamRadius), or with max_nn=m (any integer >= 1) the nearest min(n_i, m) of them -- Open3D's
+    KDTreeSearchParamHybrid(radius, max_nn = m + 1), without the 62 of k.  ONE ``search_radius(xyz, radius, capacity=capacity)``
+    serves the normals (where they are not given) and both passes; k is not read; want_idx returns the (idx, row_start, total)
+    triple.  max_nn and capacity belong to this search alone."""
     api = "compute_fpfh_feature"
     extension.check_cloud(api, "xyz", xyz)
+    if rows.radius_arguments(api, search, radius, max_nn, capacity):
+        return _compute_fpfh_radius(api, xyz, normals, radius, max_nn, capacity, want_normals, want_idx)
     grid.check_search(api, search)
     k = int(k)
     B, _, N = xyz.shape
@@ -126,4 +134,22 @@ def compute_fpfh_feature(xyz, normals=None, k=30, radius=None, want_normals=Fals
         idx = native.knn(xyz4, None, k) if search == "knn" else grid.search_knn(xyz, k)
     feat = fpfh(xyz4, idx, spfh(xyz4, normals, idx, r), r)
     res = (feat,) + ((normals,) if want_normals else ()) + ((idx,) if want_idx else ())
+    return res[0] if len(res) == 1 else res
+
+
+def _compute_fpfh_radius(api, xyz, normals, radius, max_nn, capacity, want_normals, want_idx):
+    """compute_fpfh_feature(search="radius"): one search_radius, the rows' normals where none are given, the rows' two passes."""
+    from .radius import search_radius
+    B, _, N = xyz.shape
+    if normals is not None and (not torch.is_tensor(normals) or tuple(normals.shape) != (B, 3, N)):
+        raise VcrHipError(f"{api}: normals must be [B, 3, N] like xyz {tuple(xyz.shape)}, got "
+                          f"{tuple(normals.shape) if torch.is_tensor(normals) else type(normals).__name__}")
+    if not xyz.is_cuda or (normals is not None and not normals.is_cuda):
+        raise VcrHipError(f"{api} runs on the MI355X HIP path only; move the cloud and its normals to cuda "
+                          "(there is no CPU fallback by design)")
+    csr = search_radius(xyz, radius, capacity=capacity)
+    xyz4 = native.to_rows4(xyz)
+    normals = rows.normals(xyz4, *csr, max_nn=max_nn, want_curvature=False)[0] if normals is None else normals.contiguous().float()
+    feat = rows.fpfh(xyz4, *csr, rows.spfh(xyz4, normals, *csr, max_nn=max_nn), max_nn=max_nn)
+    res = (feat,) + ((normals,) if want_normals else ()) + ((csr,) if want_idx else ())
     return res[0] if len(res) == 1 else res

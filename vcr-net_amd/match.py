@@ -181,7 +181,7 @@ def ransac_correspondences(src, tgt, corr, max_dist, trials=100000, similarity=0
 
 def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials=100000, similarity=0.9, seed=0, refine=None,
                       refine_method="point_to_point", src_normals=None, tgt_normals=None, method="ransac", fgr=None,
-                      centre=False, search="knn", nn_search="scan"):
+                      centre=False, search="knn", nn_search="scan", max_nn=None, capacity=None):
     """Register two clouds of any two sizes with neither a network nor a starting pose: src [B,3,Ns], tgt [B,3,Nt] (float32
     device tensors).  compute_fpfh_feature(k, radius) on both, match_features(mutual), ransac_correspondences(max_dist,
     trials, similarity, seed), then score_registration at max_dist on the FULL clouds (Open3D's closing evaluation).
@@ -204,17 +204,24 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     search: handed to both compute_fpfh_feature calls: "knn" is the brute-force search on the points' rows, "grid" takes the
     features' and the normals' neighbours from ``search_knn`` -- distances of differences, so the
     features need no centring, and a point excluded from its own row by its index.  It means the feature stages' kNN and
-    nothing more.
+    nothing more.  "radius" (DESIGN.md section 4.23): the features and their normals over ALL points within `radius`, or the
+    nearest max_nn of them (any max_nn >= 1: Open3D's hybrid search); radius, max_nn and capacity go to both
+    compute_fpfh_feature calls as they are, and k is not read.
     ``nn_search``: the ``search`` of the score and refine steps: "scan" (the default) or "grid", the target's uniform grid
      -- the same poses and scores bit for bit, faster on large clouds."""
-    from . import grid, gridnn
-    grid.check_search("register_features", search)
+    from . import grid, gridnn, rows
+    feat = dict(k=k, radius=radius, search=search)          # what both compute_fpfh_feature calls take
+    if rows.radius_arguments("register_features", search, radius, max_nn, capacity):
+        feat.update(max_nn=max_nn, capacity=capacity)
+    else:
+        grid.check_search("register_features", search)
     gridnn.check_search("register_features", nn_search, "nn_search")
     if centre is not False and centre is not None:
         return _register_centred(src, tgt, max_dist, centre, refine,
                                  dict(k=k, radius=radius, mutual=mutual, trials=trials, similarity=similarity, seed=seed,
                                       refine=refine, refine_method=refine_method, src_normals=src_normals,
-                                      tgt_normals=tgt_normals, method=method, fgr=fgr, search=search, nn_search=nn_search))
+                                      tgt_normals=tgt_normals, method=method, fgr=fgr, search=search, nn_search=nn_search,
+                                      max_nn=max_nn, capacity=capacity))
     from .fpfh import compute_fpfh_feature
     from .refine import refine_registration
     from .score import score_registration
@@ -224,13 +231,12 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     if method not in ("ransac", "fgr"):
         raise VcrHipError(f'{api}: method must be "ransac" or "fgr", got {method!r}')
     if method == "fgr":
-        return _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_method, src_normals, tgt_normals, fgr, search,
-                             nn_search)
+        return _register_fgr(api, src, tgt, max_dist, feat, mutual, refine, refine_method, src_normals, tgt_normals, fgr, nn_search)
     if fgr is not None:
         raise VcrHipError(f'{api}: fgr= holds the keywords of method="fgr"; the method is "ransac"')
     _ransac_checks(api, src, tgt, None, max_dist, trials, similarity, seed, given_corr=False)
-    corr = match_features(compute_fpfh_feature(src, src_normals, k=k, radius=radius, search=search),
-                          compute_fpfh_feature(tgt, tgt_normals, k=k, radius=radius, search=search), mutual=mutual)
+    corr = match_features(compute_fpfh_feature(src, src_normals, **feat), compute_fpfh_feature(tgt, tgt_normals, **feat),
+                          mutual=mutual)
     r = ransac_correspondences(src, tgt, corr, max_dist, trials, similarity, seed)
     res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist, search=nn_search))
     res.update(R=r["R"], t=r["t"], best_trial=r["best_trial"], pairs=r["pairs"], ransac_inliers=r["inliers"], corr=corr)
@@ -239,9 +245,9 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     return res
 
 
-def _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_method, src_normals, tgt_normals, kw, search="knn",
-                  nn_search="scan"):
-    """register_features with method="fgr": the same chain with fast_global_registration in the RANSAC's place."""
+def _register_fgr(api, src, tgt, max_dist, feat, mutual, refine, refine_method, src_normals, tgt_normals, kw, nn_search="scan"):
+    """register_features with method="fgr": the same chain with fast_global_registration in the RANSAC's place.  feat: the
+    keywords of both compute_fpfh_feature calls."""
     from . import fgr as F
     from .fpfh import compute_fpfh_feature
     from .refine import refine_registration
@@ -256,8 +262,8 @@ def _register_fgr(api, src, tgt, max_dist, k, radius, mutual, refine, refine_met
         raise VcrHipError(f"{api}: max_dist must be finite and >= 0, got {max_dist}")
     F._fgr_checks(api, src, tgt, None, kw["tuple_scale"], kw["max_tuples"], kw["iterations"], kw["division_factor"], kw["mu_floor"],
                   kw["tuple_trials"], kw["seed"], given_corr=False)
-    corr = match_features(compute_fpfh_feature(src, src_normals, k=k, radius=radius, search=search),
-                          compute_fpfh_feature(tgt, tgt_normals, k=k, radius=radius, search=search), mutual=mutual)
+    corr = match_features(compute_fpfh_feature(src, src_normals, **feat), compute_fpfh_feature(tgt, tgt_normals, **feat),
+                          mutual=mutual)
     r = F.fast_global_registration(src, tgt, corr, **kw)
     res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist, search=nn_search))
     res.update(R=r["R"], t=r["t"], pairs=r["pairs"], tuples=r["tuples"], used=r["used"], status=r["status"], corr=corr)

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import torch
 
-from . import extension, grid, native, refine
+from . import extension, grid, native, refine, rows
 from .native import VcrHipError, f32p, ptr
 from .score import i32p
 
@@ -67,7 +67,8 @@ def normals(xyz4, idx, viewpoint=None, want_curvature=True, guard=0, prefill=Non
     return (nrm, cur, raw) if guard or prefill is not None else (nrm, cur)
 
 
-def estimate_normals(xyz, k=20, viewpoint=None, want_curvature=False, want_idx=False, search="knn"):
+def estimate_normals(xyz, k=20, viewpoint=None, want_curvature=False, want_idx=False, search="knn", radius=None, max_nn=None,
+                     capacity=None):
     """A unit normal per point of xyz [B,3,N] (device tensor) from its k nearest neighbours: the eigenvector of the smallest
     eigenvalue of the covariance of the point and those neighbours (Open3D's estimate_normals with a kNN search), in fp64 on
     the device.  Returns normals float32 [B,3,N]; with want_curvature also the surface variation lambda0 / (lambda0 + lambda1 +
@@ -80,10 +81,21 @@ def estimate_normals(xyz, k=20, viewpoint=None, want_curvature=False, want_idx=F
     ``vcrnet_amd.centred(xyz)`` returns xyz - c and the centre c it took.
     search: "knn" is that search.  "grid" takes the neighbours from ``search_knn`` instead: distances
     of differences, so no centring is needed, and the point itself excluded by its index (among copies of a point the brute
-    force drops whichever of them came first).  The faster one for large clouds."""
+    force drops whichever of them came first).  The faster one for large clouds.
+    search="radius" (DESIGN.md section 4.23): the neighbours are ALL points within `radius` (``search_radius(xyz, radius,
+    capacity=capacity)``, rows of any length; Open3D's KDTreeSearchParamRadius), or with max_nn=m (any integer >= 1) the nearest
+    min(n_i, m) of them: Open3D's KDTreeSearchParamHybrid(radius, max_nn = m + 1) -- m counts OTHER points, as ``search_radius``
+    does.  k is not read.  A point with fewer than two neighbours gets (0, 0, 1), curvature 0.  capacity: ``search_radius``'s
+    (None reads the rows' total back once; an integer is one call without a synchronisation, and a cloud whose rows exceed it
+    comes back NaN).  want_idx then returns the (idx, row_start, total) triple in idx's place.  radius, max_nn and capacity
+    belong to this search alone."""
     if not torch.is_tensor(xyz) or xyz.dim() != 3 or xyz.shape[1] != 3:
         raise VcrHipError(f"estimate_normals: xyz must be a [B, 3, N] point cloud, got "
                           f"{tuple(xyz.shape) if torch.is_tensor(xyz) else type(xyz).__name__}")
+    if rows.radius_arguments("estimate_normals", search, radius, max_nn, capacity):
+        return _estimate_normals_radius(xyz, radius, max_nn, capacity, viewpoint, want_curvature, want_idx)
+    if radius is not None:
+        raise VcrHipError(f'estimate_normals: radius belongs to search="radius", got search={search!r}')
     grid.check_search("estimate_normals", search)
     if not xyz.is_cuda:
         raise VcrHipError("estimate_normals runs on the MI355X HIP path only; move the cloud to cuda "
@@ -101,6 +113,21 @@ def estimate_normals(xyz, k=20, viewpoint=None, want_curvature=False, want_idx=F
     idx = native.knn(xyz4, None, k) if search == "knn" else grid.search_knn(xyz, k)
     nrm, cur = normals(xyz4, idx, viewpoint, want_curvature=want_curvature)
     res = (nrm,) + ((cur,) if want_curvature else ()) + ((idx,) if want_idx else ())
+    return res[0] if len(res) == 1 else res
+
+
+def _estimate_normals_radius(xyz, radius, max_nn, capacity, viewpoint, want_curvature, want_idx):
+    """estimate_normals(search="radius"): one search_radius, then vcr_rows_normals_f32 on its rows."""
+    from .radius import search_radius
+    if not xyz.is_cuda:
+        raise VcrHipError("estimate_normals runs on the MI355X HIP path only; move the cloud to cuda "
+                          "(there is no CPU fallback by design)")
+    if viewpoint is not None and (not torch.is_tensor(viewpoint) or tuple(viewpoint.shape) != (xyz.shape[0], 3)
+                                  or not viewpoint.is_cuda):
+        raise VcrHipError(f"estimate_normals: viewpoint must be a device tensor [B, 3] with B = {xyz.shape[0]}")
+    csr = search_radius(xyz, radius, capacity=capacity)
+    nrm, cur = rows.normals(native.to_rows4(xyz), *csr, max_nn=max_nn, viewpoint=viewpoint, want_curvature=want_curvature)
+    res = (nrm,) + ((cur,) if want_curvature else ()) + ((csr,) if want_idx else ())
     return res[0] if len(res) == 1 else res
 
 
