@@ -14,7 +14,7 @@ from . import weights, synth  # noqa: F401
 __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "score_registration", "refine_registration",
            "estimate_normals", "voxel_down_sample", "remove_statistical_outlier", "remove_radius_outlier", "compute_fpfh_feature",
            "match_features", "ransac_correspondences", "register_features", "fast_global_registration", "centred",
-           "uncentred_pose", "search_knn", "search_radius"]
+           "uncentred_pose", "search_knn", "search_radius", "cluster_dbscan", "largest_cluster"]
 
 
 def __getattr__(name):
@@ -55,6 +55,9 @@ def __getattr__(name):
     if name == "search_radius":
         from .radius import search_radius
         return search_radius
+    if name in ("cluster_dbscan", "largest_cluster"):
+        from . import dbscan
+        return getattr(dbscan, name)
     if name in ("centred", "uncentred_pose"):
         from . import centre
         return getattr(centre, name)

@@ -22,6 +22,7 @@
 // The tail -- mark, offsets, write -- lives in outlier_tail.h, which radius.hip includes too (the radius filter on the grid).
 // No atomics, no scratch, no loop whose trip count depends on anything but N, k, S and a tile index.
 #include "outlier_tail.h"
+#include "outlier_flags.h"
 
 namespace {
 
@@ -346,4 +347,15 @@ extern "C" int vcr_outlier_radius_f32(const vcr_outlier_radius_args* ua, void* w
   if ((e = VCR_LAUNCH_RC())) return e;
   const OlTail tl{nullptr, nullptr, cnt, a.nb_points, nullptr, a.xyz, a.N, p.scan.nblk, blk, a.points, a.count, a.index};
   return ol_compact(tl, a.B, p.point_grid, s);
+}
+
+// The tail alone, on keep flags the caller computed (outlier_flags.h): a flag is a count held against nb_points = 0
+int outlier_compact_flags(const int* flags, const float* xyz, int B, int N, int* blkcnt, float* points, int* count, int* index,
+                          hipStream_t s) {
+  const int nblk = (N + NN_BLOCK - 1) / NN_BLOCK;
+  const unsigned point_grid = (unsigned)((long)B * nblk);
+  const OlTail tl{nullptr, nullptr, flags, 0, nullptr, xyz, N, nblk, blkcnt, points, count, index};
+  hipLaunchKernelGGL(outlier_mark_kernel, dim3(point_grid), dim3(NN_BLOCK), 0, s, tl);
+  const int e = VCR_LAUNCH_RC();
+  return e ? e : ol_compact(tl, B, point_grid, s);
 }
