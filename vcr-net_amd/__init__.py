@@ -14,7 +14,8 @@ from . import weights, synth  # noqa: F401
 __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "score_registration", "refine_registration",
            "estimate_normals", "voxel_down_sample", "remove_statistical_outlier", "remove_radius_outlier", "compute_fpfh_feature",
            "match_features", "ransac_correspondences", "register_features", "fast_global_registration", "centred",
-           "uncentred_pose", "search_knn", "search_radius", "cluster_dbscan", "largest_cluster"]
+           "uncentred_pose", "search_knn", "search_radius", "cluster_dbscan", "largest_cluster", "segment_plane",
+           "split_by_plane", "segment_planes"]
 
 
 def __getattr__(name):
@@ -58,6 +59,9 @@ def __getattr__(name):
     if name in ("cluster_dbscan", "largest_cluster"):
         from . import dbscan
         return getattr(dbscan, name)
+    if name in ("segment_plane", "split_by_plane", "segment_planes"):
+        from . import segment
+        return getattr(segment, name)
     if name in ("centred", "uncentred_pose"):
         from . import centre
         return getattr(centre, name)
