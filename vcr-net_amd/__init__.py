@@ -15,7 +15,7 @@ __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "sco
            "estimate_normals", "voxel_down_sample", "remove_statistical_outlier", "remove_radius_outlier", "compute_fpfh_feature",
            "match_features", "ransac_correspondences", "register_features", "fast_global_registration", "centred",
            "uncentred_pose", "search_knn", "search_radius", "cluster_dbscan", "largest_cluster", "segment_plane",
-           "split_by_plane", "segment_planes"]
+           "split_by_plane", "segment_planes", "orient_normals_consistent_tangent_plane"]
 
 
 def __getattr__(name):
@@ -62,6 +62,9 @@ def __getattr__(name):
     if name in ("segment_plane", "split_by_plane", "segment_planes"):
         from . import segment
         return getattr(segment, name)
+    if name == "orient_normals_consistent_tangent_plane":
+        from .orient import orient_normals_consistent_tangent_plane
+        return orient_normals_consistent_tangent_plane
     if name in ("centred", "uncentred_pose"):
         from . import centre
         return getattr(centre, name)

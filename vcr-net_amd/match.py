@@ -181,15 +181,27 @@ def ransac_correspondences(src, tgt, corr, max_dist, trials=100000, similarity=0
 
 def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials=100000, similarity=0.9, seed=0, refine=None,
                       refine_method="point_to_point", src_normals=None, tgt_normals=None, method="ransac", fgr=None,
-                      centre=False, search="knn", nn_search="scan", max_nn=None, capacity=None):
+                      centre=False, search="knn", nn_search="scan", max_nn=None, capacity=None, orient=None, orient_k=12):
     """Register two clouds of any two sizes with neither a network nor a starting pose: src [B,3,Ns], tgt [B,3,Nt] (float32
     device tensors).  compute_fpfh_feature(k, radius) on both, match_features(mutual), ransac_correspondences(max_dist,
     trials, similarity, seed), then score_registration at max_dist on the FULL clouds (Open3D's closing evaluation).
     refine: a correspondence cap; refine_registration(method=refine_method, max_dist=refine) then runs from the RANSAC's pose.
     src_normals, tgt_normals [B,3,N]: the clouds' normals for the features; None estimates them (estimate_normals, from the
     features' own search).  An estimated normal's SIGN is arbitrary, and the feature of a point changes with it: two copies of
-    one surface match far better with normals oriented alike (towards the sensor, say) than with estimated ones -- on the
-    test's surface 99.7 % of the one-way matches are the true partner against 18 % at 600 points.
+    one surface match far better with normals oriented alike than with estimated ones -- on the test's surface 99.7 % of the
+    one-way matches are the true partner against 18 % at 600 points.  Two remedies: normals oriented
+    towards a sensor position where one is known (``estimate_normals(viewpoint=)``), or orient="tangent" where none is -- a
+    registered scan, a merged cloud, a mesh sample.
+    orient: None uses the normals as they are.  "tangent" (DESIGN.md section 4.26): every side whose normals are ESTIMATED has
+    them oriented by ``orient_normals_consistent_tangent_plane(k=orient_k)`` before its features are computed; given normals
+    are used as they are.  That leaves one global sign per cloud, so where at least one side was estimated the chain --
+    features, matching, RANSAC or FGR, score -- runs TWICE, once with the source's normals as oriented and once with all of
+    them negated, and per cloud the run with the higher fitness is kept on the device -- where the fitness is equal the one
+    with the lower inlier_rmse (two runs that both end with every point an inlier differ there by orders of magnitude), and
+    the oriented run among equals --: every key of the dict is selected per cloud, `flipped` bool [B] says which run it was,
+    and refine runs once, from the kept pose.
+    The second run costs the source's features, the matching, the RANSAC or FGR and a score again (DESIGN.md section 4.26
+    states it as measured).
     method: "ransac", or "fgr": fast_global_registration (``fgr``) takes the RANSAC's place -- no trial
     budget; trials, similarity and seed are not used, `fgr` is a dict of its keywords (tuple_scale, max_tuples, iterations,
     division_factor, mu_floor, decrease_mu, tuple_trials, seed).  The score and refine work from its pose in the same way.
@@ -216,12 +228,16 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     else:
         grid.check_search("register_features", search)
     gridnn.check_search("register_features", nn_search, "nn_search")
+    if orient not in (None, "tangent"):
+        raise VcrHipError(f'register_features: orient must be None or "tangent", got {orient!r}')
+    if isinstance(orient_k, bool) or not isinstance(orient_k, int) or orient_k < 1:
+        raise VcrHipError(f"register_features: orient_k must be an integer >= 1, got {orient_k!r}")
     if centre is not False and centre is not None:
         return _register_centred(src, tgt, max_dist, centre, refine,
                                  dict(k=k, radius=radius, mutual=mutual, trials=trials, similarity=similarity, seed=seed,
                                       refine=refine, refine_method=refine_method, src_normals=src_normals,
                                       tgt_normals=tgt_normals, method=method, fgr=fgr, search=search, nn_search=nn_search,
-                                      max_nn=max_nn, capacity=capacity))
+                                      max_nn=max_nn, capacity=capacity, orient=orient, orient_k=orient_k))
     from .fpfh import compute_fpfh_feature
     from .refine import refine_registration
     from .score import score_registration
@@ -231,21 +247,64 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     if method not in ("ransac", "fgr"):
         raise VcrHipError(f'{api}: method must be "ransac" or "fgr", got {method!r}')
     if method == "fgr":
-        return _register_fgr(api, src, tgt, max_dist, feat, mutual, refine, refine_method, src_normals, tgt_normals, fgr, nn_search)
+        return _register_fgr(api, src, tgt, max_dist, feat, mutual, refine, refine_method, src_normals, tgt_normals, fgr, nn_search,
+                             orient, orient_k)
     if fgr is not None:
         raise VcrHipError(f'{api}: fgr= holds the keywords of method="fgr"; the method is "ransac"')
     _ransac_checks(api, src, tgt, None, max_dist, trials, similarity, seed, given_corr=False)
-    corr = match_features(compute_fpfh_feature(src, src_normals, **feat), compute_fpfh_feature(tgt, tgt_normals, **feat),
-                          mutual=mutual)
-    r = ransac_correspondences(src, tgt, corr, max_dist, trials, similarity, seed)
-    res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist, search=nn_search))
-    res.update(R=r["R"], t=r["t"], best_trial=r["best_trial"], pairs=r["pairs"], ransac_inliers=r["inliers"], corr=corr)
+
+    def tail(src_feat, tgt_feat):
+        corr = match_features(src_feat, tgt_feat, mutual=mutual)
+        r = ransac_correspondences(src, tgt, corr, max_dist, trials, similarity, seed)
+        res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist, search=nn_search))
+        res.update(R=r["R"], t=r["t"], best_trial=r["best_trial"], pairs=r["pairs"], ransac_inliers=r["inliers"], corr=corr)
+        return res
+    res = _both_signs(src, tgt, src_normals, tgt_normals, feat, orient, orient_k, tail)
     if refine is not None:
-        res["refined"] = refine_registration(src, tgt, r["R"], r["t"], float(refine), method=refine_method, search=nn_search)
+        res["refined"] = refine_registration(src, tgt, res["R"], res["t"], float(refine), method=refine_method, search=nn_search)
     return res
 
 
-def _register_fgr(api, src, tgt, max_dist, feat, mutual, refine, refine_method, src_normals, tgt_normals, kw, nn_search="scan"):
+def _estimated_normals(xyz, feat):
+    """The normals compute_fpfh_feature(xyz, None, **feat) estimates for itself, bit for bit: the same call on the same search."""
+    from .plane import estimate_normals
+    if feat["search"] == "radius":
+        return estimate_normals(xyz, search="radius", radius=feat["radius"], max_nn=feat["max_nn"], capacity=feat["capacity"])
+    return estimate_normals(xyz, feat["k"], search=feat["search"])
+
+
+def _both_signs(src, tgt, src_normals, tgt_normals, feat, orient, orient_k, tail):
+    """The features of both clouds (feat: the keywords of both compute_fpfh_feature calls) and tail(src_feat, tgt_feat) -> the
+    result's dict: matching, RANSAC or FGR, score.  orient="tangent": a side without given normals has them estimated and
+    oriented first; where there is such a side the tail runs a second time on the features of the source's normals negated, and
+    every entry is taken per cloud from the run with the higher fitness -- the lower inlier_rmse where the fitness is equal --,
+    the first among equals; `flipped` bool [B]."""
+    from .fpfh import compute_fpfh_feature
+    if orient is None:
+        return tail(compute_fpfh_feature(src, src_normals, **feat), compute_fpfh_feature(tgt, tgt_normals, **feat))
+    from .orient import orient_normals_consistent_tangent_plane
+    twice = src_normals is None or tgt_normals is None
+    if src_normals is None:
+        src_normals = orient_normals_consistent_tangent_plane(src, _estimated_normals(src, feat), k=orient_k)
+    if tgt_normals is None:
+        tgt_normals = orient_normals_consistent_tangent_plane(tgt, _estimated_normals(tgt, feat), k=orient_k)
+    src_feat, tgt_feat = compute_fpfh_feature(src, src_normals, **feat), compute_fpfh_feature(tgt, tgt_normals, **feat)
+    res = tail(src_feat, tgt_feat)
+    flipped = torch.zeros(src.shape[0], dtype=torch.bool, device=res["fitness"].device)
+    if twice:
+        other = tail(compute_fpfh_feature(src, -src_normals, **feat), tgt_feat)
+        # fitness first, then the lower inlier_rmse (Open3D's order of two RANSAC results): on clean copies BOTH runs can end
+        # with every point an inlier -- a few correct matches among many wrong ones still find a pose -- and the fitness ties
+        flipped = (other["fitness"] > res["fitness"]) | ((other["fitness"] == res["fitness"])
+                                                         & (other["inlier_rmse"] < res["inlier_rmse"]))
+        for key, a in res.items():
+            res[key] = torch.where(flipped.view((-1,) + (1,) * (a.dim() - 1)), other[key], a)
+    res["flipped"] = flipped
+    return res
+
+
+def _register_fgr(api, src, tgt, max_dist, feat, mutual, refine, refine_method, src_normals, tgt_normals, kw, nn_search="scan",
+                  orient=None, orient_k=12):
     """register_features with method="fgr": the same chain with fast_global_registration in the RANSAC's place.  feat: the
     keywords of both compute_fpfh_feature calls."""
     from . import fgr as F
@@ -262,13 +321,16 @@ def _register_fgr(api, src, tgt, max_dist, feat, mutual, refine, refine_method, 
         raise VcrHipError(f"{api}: max_dist must be finite and >= 0, got {max_dist}")
     F._fgr_checks(api, src, tgt, None, kw["tuple_scale"], kw["max_tuples"], kw["iterations"], kw["division_factor"], kw["mu_floor"],
                   kw["tuple_trials"], kw["seed"], given_corr=False)
-    corr = match_features(compute_fpfh_feature(src, src_normals, **feat), compute_fpfh_feature(tgt, tgt_normals, **feat),
-                          mutual=mutual)
-    r = F.fast_global_registration(src, tgt, corr, **kw)
-    res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist, search=nn_search))
-    res.update(R=r["R"], t=r["t"], pairs=r["pairs"], tuples=r["tuples"], used=r["used"], status=r["status"], corr=corr)
+
+    def tail(src_feat, tgt_feat):
+        corr = match_features(src_feat, tgt_feat, mutual=mutual)
+        r = F.fast_global_registration(src, tgt, corr, **kw)
+        res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist, search=nn_search))
+        res.update(R=r["R"], t=r["t"], pairs=r["pairs"], tuples=r["tuples"], used=r["used"], status=r["status"], corr=corr)
+        return res
+    res = _both_signs(src, tgt, src_normals, tgt_normals, feat, orient, orient_k, tail)
     if refine is not None:
-        res["refined"] = refine_registration(src, tgt, r["R"], r["t"], float(refine), method=refine_method, search=nn_search)
+        res["refined"] = refine_registration(src, tgt, res["R"], res["t"], float(refine), method=refine_method, search=nn_search)
     return res
 
 

@@ -74,7 +74,7 @@ def estimate_normals(xyz, k=20, viewpoint=None, want_curvature=False, want_idx=F
     the device.  Returns normals float32 [B,3,N]; with want_curvature also the surface variation lambda0 / (lambda0 + lambda1 +
     lambda2), float32 [B,N]; with want_idx also the neighbours, int32 [B,N,k] -- as a tuple in that order.
     viewpoint [B,3]: every normal looks at it (n . (viewpoint - x) >= 0); None: the component of largest magnitude is positive.
-    No orientation is propagated between points.
+    No orientation is propagated between points here: ``orient_normals_consistent_tangent_plane`` does that.
     The neighbours are the library's kNN (native.knn on the points' rows, ties broken exactly), whose distance is the expansion
     2 x.y - |x|^2 - |y|^2 in fp32: for a cloud far from the origin relative to its spacing it cancels, and the neighbours are
     then not the nearest.  Centre such a cloud first (normals do not change under a translation):
