@@ -15,7 +15,8 @@ __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "sco
            "estimate_normals", "voxel_down_sample", "remove_statistical_outlier", "remove_radius_outlier", "compute_fpfh_feature",
            "match_features", "ransac_correspondences", "register_features", "fast_global_registration", "centred",
            "uncentred_pose", "search_knn", "search_radius", "cluster_dbscan", "largest_cluster", "segment_plane",
-           "split_by_plane", "segment_planes", "orient_normals_consistent_tangent_plane"]
+           "split_by_plane", "segment_planes", "orient_normals_consistent_tangent_plane", "compute_iss_keypoints",
+           "model_resolution"]
 
 
 def __getattr__(name):
@@ -65,6 +66,9 @@ def __getattr__(name):
     if name == "orient_normals_consistent_tangent_plane":
         from .orient import orient_normals_consistent_tangent_plane
         return orient_normals_consistent_tangent_plane
+    if name in ("compute_iss_keypoints", "model_resolution"):
+        from . import iss
+        return getattr(iss, name)
     if name in ("centred", "uncentred_pose"):
         from . import centre
         return getattr(centre, name)

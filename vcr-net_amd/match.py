@@ -181,7 +181,8 @@ def ransac_correspondences(src, tgt, corr, max_dist, trials=100000, similarity=0
 
 def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials=100000, similarity=0.9, seed=0, refine=None,
                       refine_method="point_to_point", src_normals=None, tgt_normals=None, method="ransac", fgr=None,
-                      centre=False, search="knn", nn_search="scan", max_nn=None, capacity=None, orient=None, orient_k=12):
+                      centre=False, search="knn", nn_search="scan", max_nn=None, keypoints=None, iss=None, capacity=None,
+                      orient=None, orient_k=12):
     """Register two clouds of any two sizes with neither a network nor a starting pose: src [B,3,Ns], tgt [B,3,Nt] (float32
     device tensors).  compute_fpfh_feature(k, radius) on both, match_features(mutual), ransac_correspondences(max_dist,
     trials, similarity, seed), then score_registration at max_dist on the FULL clouds (Open3D's closing evaluation).
@@ -220,7 +221,12 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     nearest max_nn of them (any max_nn >= 1: Open3D's hybrid search); radius, max_nn and capacity go to both
     compute_fpfh_feature calls as they are, and k is not read.
     ``nn_search``: the ``search`` of the score and refine steps: "scan" (the default) or "grid", the target's uniform grid
-     -- the same poses and scores bit for bit, faster on large clouds."""
+     -- the same poses and scores bit for bit, faster on large clouds.
+    keypoints: None matches every source point.  "iss" (DESIGN.md section 4.27): ``compute_iss_keypoints(src, **iss)`` -- `iss` a
+    dict of its keywords (salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, capacity, cell) -- picks the source's
+    keypoints, and directly behind match_features corr[b, i] becomes -1 where source point i is not one: the RANSAC or FGR
+    draws from the keypoints' pairs alone.  The features are still computed on the whole clouds and the target is searched
+    whole; the score and refine steps use every point.  Under orient="tangent" both runs take the same mask."""
     from . import grid, gridnn, rows
     feat = dict(k=k, radius=radius, search=search)          # what both compute_fpfh_feature calls take
     if rows.radius_arguments("register_features", search, radius, max_nn, capacity):
@@ -232,12 +238,14 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
         raise VcrHipError(f'register_features: orient must be None or "tangent", got {orient!r}')
     if isinstance(orient_k, bool) or not isinstance(orient_k, int) or orient_k < 1:
         raise VcrHipError(f"register_features: orient_k must be an integer >= 1, got {orient_k!r}")
+    iss = _keypoint_arguments("register_features", keypoints, iss)
     if centre is not False and centre is not None:
         return _register_centred(src, tgt, max_dist, centre, refine,
                                  dict(k=k, radius=radius, mutual=mutual, trials=trials, similarity=similarity, seed=seed,
                                       refine=refine, refine_method=refine_method, src_normals=src_normals,
                                       tgt_normals=tgt_normals, method=method, fgr=fgr, search=search, nn_search=nn_search,
-                                      max_nn=max_nn, capacity=capacity, orient=orient, orient_k=orient_k))
+                                      max_nn=max_nn, capacity=capacity, orient=orient, orient_k=orient_k,
+                                      keypoints=keypoints, iss=iss or None))
     from .fpfh import compute_fpfh_feature
     from .refine import refine_registration
     from .score import score_registration
@@ -248,13 +256,14 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
         raise VcrHipError(f'{api}: method must be "ransac" or "fgr", got {method!r}')
     if method == "fgr":
         return _register_fgr(api, src, tgt, max_dist, feat, mutual, refine, refine_method, src_normals, tgt_normals, fgr, nn_search,
-                             orient, orient_k)
+                             orient, orient_k, keypoints, iss)
     if fgr is not None:
         raise VcrHipError(f'{api}: fgr= holds the keywords of method="fgr"; the method is "ransac"')
     _ransac_checks(api, src, tgt, None, max_dist, trials, similarity, seed, given_corr=False)
+    keep = _keypoint_mask(src, keypoints, iss)
 
     def tail(src_feat, tgt_feat):
-        corr = match_features(src_feat, tgt_feat, mutual=mutual)
+        corr = _masked(match_features(src_feat, tgt_feat, mutual=mutual), keep)
         r = ransac_correspondences(src, tgt, corr, max_dist, trials, similarity, seed)
         res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist, search=nn_search))
         res.update(R=r["R"], t=r["t"], best_trial=r["best_trial"], pairs=r["pairs"], ransac_inliers=r["inliers"], corr=corr)
@@ -263,6 +272,41 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     if refine is not None:
         res["refined"] = refine_registration(src, tgt, res["R"], res["t"], float(refine), method=refine_method, search=nn_search)
     return res
+
+
+ISS_KEYWORDS = ("salient_radius", "non_max_radius", "gamma_21", "gamma_32", "min_neighbors", "capacity", "cell")
+
+
+def _keypoint_arguments(api, keypoints, iss):
+    """What register_features asks of (keypoints, iss) in front of everything else -> iss as a dict."""
+    if keypoints not in (None, "iss") or isinstance(keypoints, bool):
+        raise VcrHipError(f'{api}: keypoints must be None or "iss", got {keypoints!r}')
+    if iss is not None and (not isinstance(iss, dict) or set(iss) - set(ISS_KEYWORDS)):
+        raise VcrHipError(f"{api}: iss must be None or a dict with keys among {sorted(ISS_KEYWORDS)}, got "
+                          f"{sorted(iss) if isinstance(iss, dict) else type(iss).__name__}")
+    if iss is not None and keypoints is None:
+        raise VcrHipError(f'{api}: iss= holds the keywords of keypoints="iss"; keypoints is None')
+    iss = {} if iss is None else dict(iss)
+    if keypoints is not None:
+        from .iss import check_arguments
+        check_arguments(api, **iss)
+    return iss
+
+
+def _keypoint_mask(src, keypoints, iss):
+    """bool [B,Ns]: the source points that keep their match; None where every point does."""
+    if keypoints is None:
+        return None
+    from .iss import compute_iss_keypoints
+    try:
+        return compute_iss_keypoints(src, want_flag=True, **iss)[3] > 0
+    except VcrHipError as e:
+        raise VcrHipError(str(e).replace("compute_iss_keypoints", 'register_features (keypoints="iss")', 1)) from None
+
+
+def _masked(corr, keep):
+    """match_features' corr with -1 (no partner) where keep is False: a device `where`."""
+    return corr if keep is None else torch.where(keep, corr, torch.full_like(corr, -1))
 
 
 def _estimated_normals(xyz, feat):
@@ -304,7 +348,7 @@ def _both_signs(src, tgt, src_normals, tgt_normals, feat, orient, orient_k, tail
 
 
 def _register_fgr(api, src, tgt, max_dist, feat, mutual, refine, refine_method, src_normals, tgt_normals, kw, nn_search="scan",
-                  orient=None, orient_k=12):
+                  orient=None, orient_k=12, keypoints=None, iss=None):
     """register_features with method="fgr": the same chain with fast_global_registration in the RANSAC's place.  feat: the
     keywords of both compute_fpfh_feature calls."""
     from . import fgr as F
@@ -321,9 +365,10 @@ def _register_fgr(api, src, tgt, max_dist, feat, mutual, refine, refine_method, 
         raise VcrHipError(f"{api}: max_dist must be finite and >= 0, got {max_dist}")
     F._fgr_checks(api, src, tgt, None, kw["tuple_scale"], kw["max_tuples"], kw["iterations"], kw["division_factor"], kw["mu_floor"],
                   kw["tuple_trials"], kw["seed"], given_corr=False)
+    keep = _keypoint_mask(src, keypoints, iss)
 
     def tail(src_feat, tgt_feat):
-        corr = match_features(src_feat, tgt_feat, mutual=mutual)
+        corr = _masked(match_features(src_feat, tgt_feat, mutual=mutual), keep)
         r = F.fast_global_registration(src, tgt, corr, **kw)
         res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist, search=nn_search))
         res.update(R=r["R"], t=r["t"], pairs=r["pairs"], tuples=r["tuples"], used=r["used"], status=r["status"], corr=corr)
