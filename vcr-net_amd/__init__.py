@@ -16,7 +16,7 @@ __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "sco
            "match_features", "ransac_correspondences", "register_features", "fast_global_registration", "centred",
            "uncentred_pose", "search_knn", "search_radius", "cluster_dbscan", "largest_cluster", "segment_plane",
            "split_by_plane", "segment_planes", "orient_normals_consistent_tangent_plane", "compute_iss_keypoints",
-           "model_resolution"]
+           "model_resolution", "compute_point_cloud_distance"]
 
 
 def __getattr__(name):
@@ -69,6 +69,9 @@ def __getattr__(name):
     if name in ("compute_iss_keypoints", "model_resolution"):
         from . import iss
         return getattr(iss, name)
+    if name == "compute_point_cloud_distance":
+        from .query import compute_point_cloud_distance
+        return compute_point_cloud_distance
     if name in ("centred", "uncentred_pose"):
         from . import centre
         return getattr(centre, name)

@@ -28,6 +28,7 @@ DBSCAN_HEADERS = [os.path.join(INCLUDE, "cluster", f) for f in ("vcr_hip_dbscan.
 SEGMENT_HEADERS = [os.path.join(INCLUDE, "segment", f) for f in ("vcr_hip_segment.h",)]   # (... and include/cluster/'s)
 ORIENT_HEADERS = [os.path.join(INCLUDE, "orient", f) for f in ("vcr_hip_orient.h",)]   # (... and include/segment/'s)
 ISS_HEADERS = [os.path.join(INCLUDE, "keypoint", f) for f in ("vcr_hip_iss.h",)]   # (... and include/orient/'s)
+QUERY_HEADERS = [os.path.join(INCLUDE, "query", f) for f in ("vcr_hip_query.h",)]   # (... and include/keypoint/'s)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off"]   # no silent a*b+c fusion: the kernels spell out every fmaf they want
@@ -43,7 +44,7 @@ def sources_sha16() -> str:
     import hashlib
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h")))
-    files += PUBLIC_HEADERS + LATER_HEADERS + OUTLIER_HEADERS + GICP_HEADERS + FPFH_HEADERS + MATCH_HEADERS + FGR_HEADERS + GRID_HEADERS + GRIDNN_HEADERS + VOXEL_SORT_HEADERS + RADIUS_HEADERS + ROWS_HEADERS + DBSCAN_HEADERS + SEGMENT_HEADERS + ORIENT_HEADERS + ISS_HEADERS
+    files += PUBLIC_HEADERS + LATER_HEADERS + OUTLIER_HEADERS + GICP_HEADERS + FPFH_HEADERS + MATCH_HEADERS + FGR_HEADERS + GRID_HEADERS + GRIDNN_HEADERS + VOXEL_SORT_HEADERS + RADIUS_HEADERS + ROWS_HEADERS + DBSCAN_HEADERS + SEGMENT_HEADERS + ORIENT_HEADERS + ISS_HEADERS + QUERY_HEADERS
     for f in files:
         h.update(os.path.basename(f).encode())
         with open(f, "rb") as fh:
@@ -98,7 +99,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     GPU box -- may reorder mtimes, and must neither trigger a rebuild there nor hide one that is needed."""
     os.makedirs(OBJ, exist_ok=True)
     hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
-    hdrs += PUBLIC_HEADERS + LATER_HEADERS + OUTLIER_HEADERS + GICP_HEADERS + FPFH_HEADERS + MATCH_HEADERS + FGR_HEADERS + GRID_HEADERS + GRIDNN_HEADERS + VOXEL_SORT_HEADERS + RADIUS_HEADERS + ROWS_HEADERS + DBSCAN_HEADERS + SEGMENT_HEADERS + ORIENT_HEADERS + ISS_HEADERS
+    hdrs += PUBLIC_HEADERS + LATER_HEADERS + OUTLIER_HEADERS + GICP_HEADERS + FPFH_HEADERS + MATCH_HEADERS + FGR_HEADERS + GRID_HEADERS + GRIDNN_HEADERS + VOXEL_SORT_HEADERS + RADIUS_HEADERS + ROWS_HEADERS + DBSCAN_HEADERS + SEGMENT_HEADERS + ORIENT_HEADERS + ISS_HEADERS + QUERY_HEADERS
     flags = " ".join(FLAGS)
     jobs, want = [], {}
     for src in sources():

@@ -82,7 +82,7 @@ def grid_knn(xyz, k, cell=0.0, want_d2=True, variant=0, guard=0, prefill=None):
     return o
 
 
-def search_knn(xyz, k, want_d2=False, cell=None):
+def search_knn(xyz, k, want_d2=False, cell=None, queries=None):
     """The k nearest neighbours of every point of xyz [B,3,N] (device tensor, up to 131 072 points a cloud) among the cloud's
     other points, exactly: int32 [B,N,k], per point in ascending order of (distance, index); with want_d2 also the squared
     distances, float32 [B,N,k], as a tuple (idx, d2).  No host synchronisation.  1 <= k <= 62 and k + 1 <= N.
@@ -91,11 +91,22 @@ def search_knn(xyz, k, want_d2=False, cell=None):
     is excluded from its own row by its index: copies of it are neighbours at distance 0.  A point with a NaN or infinite
     coordinate is nobody's neighbour, and its own row -- like every slot a row cannot fill -- holds its own index and +inf.
     The search walks a uniform grid built on the device; cell forces the grid's edge (None: chosen from
-    the cloud's bounds), which changes the time and never the result."""
+    the cloud's bounds), which changes the time and never the result.
+    queries=[B,3,M] (device tensor, up to 131 072 positions a cloud) asks about THOSE positions instead of the cloud's own
+    points: int32 [B,M,k] (and float32 [B,M,k]), the k nearest points of xyz to every query in the same order and arithmetic
+    (DESIGN.md section 4.28).  A query is a position, not an index: a point that coincides with it is its first neighbour at
+    distance 0.  k may exceed N: a slot a row cannot fill -- and every slot of a query with a NaN or infinite coordinate --
+    holds -1 and +inf.  E.g. carrying labels from a down-sampled cloud back to the full one:
+        down, count, _ = voxel_down_sample(full, voxel)        # (NaN behind count[b]: in nobody's row)
+        labels, _ = cluster_dbscan(down, eps, min_points)
+        nearest = search_knn(down, 1, queries=full)[:, :, 0]
+        full_labels = torch.where(nearest >= 0, labels.gather(1, nearest.clamp(min=0).long()), -1)"""
     api = "search_knn"
     extension.check_cloud(api, "xyz", xyz)
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
         raise VcrHipError(f"{api}: k must be an integer in [1, {MAX_K}], got {k!r}")
+    if queries is not None:
+        return _search_queries(api, xyz, queries, k, want_d2, cell)
     N = xyz.shape[2]
     if k + 1 > N:
         raise VcrHipError(f"{api}: k + 1 = {k + 1} neighbours need at least as many points, got N = {N}")
@@ -106,4 +117,16 @@ def search_knn(xyz, k, want_d2=False, cell=None):
         if not (math.isfinite(cell) and cell > 0.0):
             raise VcrHipError(f"{api}: cell must be None (the automatic grid) or finite and > 0, got {cell}")
     o = grid_knn(xyz, k, 0.0 if cell is None else cell, want_d2=want_d2)
+    return (o["idx"], o["d2"]) if want_d2 else o["idx"]
+
+
+def _search_queries(api, xyz, queries, k, want_d2, cell):
+    """search_knn's cross search: the rows of the positions `queries` among the points xyz (query.grid_knn)."""
+    from . import query
+    query._pair(api, xyz, queries)
+    if cell is not None:
+        cell = float(cell)
+        if not (math.isfinite(cell) and cell > 0.0):
+            raise VcrHipError(f"{api}: cell must be None (the automatic grid) or finite and > 0, got {cell}")
+    o = query.grid_knn(xyz, queries, k, 0.0 if cell is None else cell, want_d2=want_d2)
     return (o["idx"], o["d2"]) if want_d2 else o["idx"]

@@ -158,10 +158,10 @@ def radius_filter_grid(xyz, radius, nb_points, cell=0.0, order=0, want_trace=Tru
     return o
 
 
-def _hybrid(xyz, r2, m, want_d2, cell, capacity):
+def _hybrid(xyz, r2, m, want_d2, cell, capacity, queries=None):
     """The first min(n_i, m) entries of every radius row, from search_knn's rows cut at r2 and compacted to CSR by torch ops."""
     api = "search_radius"
-    idx, d2 = grid.search_knn(xyz, m, want_d2=True, cell=cell)
+    idx, d2 = grid.search_knn(xyz, m, want_d2=True, cell=cell, queries=queries)
     B, N, _ = idx.shape
     hit = d2 <= r2                                          # (a short row's slots hold +inf; the rows ascend: a prefix)
     count = hit.sum(dim=2)
@@ -188,7 +188,7 @@ def _hybrid(xyz, r2, m, want_d2, cell, capacity):
     return out_idx, row_start, total, flat_d2[:B * capacity].view(B, capacity)
 
 
-def search_radius(xyz, radius, max_nn=None, want_d2=False, cell=None, capacity=None):
+def search_radius(xyz, radius, max_nn=None, want_d2=False, cell=None, capacity=None, queries=None):
     """ALL points within radius of every point of xyz [B,3,N] (device tensor, up to 131 072 points a cloud) among the cloud's
     other points, exactly: Open3D's search_radius_vector_3d for every point at once.  Returns (idx, row_start, total), with
     want_d2 (idx, row_start, total, d2):
@@ -208,15 +208,22 @@ def search_radius(xyz, radius, max_nn=None, want_d2=False, cell=None, capacity=N
     min(n_i, m) entries, row_start and total those of the cut rows.  It is served from ``search_knn(xyz, m)``.
     The rows are ordered by a rank sort whose cost is quadratic in a row's length: meant for neighbourhoods.
     The search walks a uniform grid built on the device whose edge is the radius; cell forces another
-    edge, which changes the time and never the result."""
+    edge, which changes the time and never the result.
+    queries=[B,3,M] (device tensor, up to 131 072 positions a cloud) asks about THOSE positions instead of the cloud's own
+    points: the same outputs with M for N -- row_start is [B,M+1], row i holds the points of xyz within
+    radius of query i.  A query is a position, not an index: nothing is excluded, and a point that coincides with a query heads
+    its row at distance 0.  A query with a NaN or infinite coordinate has an empty row.  max_nn=m needs no m + 1 <= N there."""
     api = "search_radius"
     _cloud(api, xyz)
+    if queries is not None:
+        from . import query
+        query._pair(api, xyz, queries)
     radius, r2 = _radius(api, radius)
     B, _, N = xyz.shape
     if max_nn is not None:
         if isinstance(max_nn, bool) or not isinstance(max_nn, int) or not 1 <= max_nn <= MAX_NN:
             raise VcrHipError(f"{api}: max_nn must be None or an integer in [1, {MAX_NN}], got {max_nn!r}")
-        if max_nn + 1 > N:
+        if queries is None and max_nn + 1 > N:
             raise VcrHipError(f"{api}: max_nn + 1 = {max_nn + 1} neighbours need at least as many points, got N = {N}")
     if capacity is not None:
         if isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 0:
@@ -231,13 +238,20 @@ def search_radius(xyz, radius, max_nn=None, want_d2=False, cell=None, capacity=N
         if not (math.isfinite(cell) and cell > 0.0):
             raise VcrHipError(f"{api}: cell must be None (the radius) or finite and > 0, got {cell!r}")
     _on_device(api, xyz)
+    if queries is not None:
+        query._on_device(api, xyz, queries)
     if max_nn is not None:
-        return _hybrid(xyz, r2, max_nn, want_d2, cell, capacity)
+        return _hybrid(xyz, r2, max_nn, want_d2, cell, capacity, queries)
     cell = 0.0 if cell is None else cell
+    if queries is None:
+        search = grid_radius
+    else:
+        def search(xyz, *a, **kw):
+            return query.grid_radius(xyz, queries, *a, **kw)
     if capacity is None:
-        counted = grid_radius(xyz, radius, 0, want_idx=False, cell=cell)
+        counted = search(xyz, radius, 0, want_idx=False, cell=cell)
         capacity = int(counted["total"].max())             # the ONE host synchronisation
         if B * capacity >= _INT32_LIMIT:
             raise VcrHipError(f"{api}: the rows need B * {capacity} slots, beyond 2^31: search the clouds one at a time")
-    o = grid_radius(xyz, radius, capacity, want_idx=True, want_d2=want_d2, cell=cell)
+    o = search(xyz, radius, capacity, want_idx=True, want_d2=want_d2, cell=cell)
     return (o["idx"], o["row_start"], o["total"], o["d2"]) if want_d2 else (o["idx"], o["row_start"], o["total"])
