@@ -101,7 +101,7 @@ def kernel_split(fn, calls=5):
         torch.cuda.synchronize()
     split = {}
     for e in prof.key_averages():
-        m = re.search(r"((?:grid|radius|query)_\w+_kernel)", e.key)
+        m = re.search(r"((?:grid|radius|rows|query)_\w+_kernel)", e.key)
         if m:
             t = getattr(e, "device_time_total", getattr(e, "cuda_time_total", 0.0)) / 1e3 / calls
             split[m.group(1)] = split.get(m.group(1), 0.0) + t

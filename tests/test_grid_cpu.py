@@ -5,6 +5,7 @@ against a fractions.Fraction one, and the walk -- faces, cells by comparison, ri
 brute-force definition, row for row and bit for bit."""
 import ctypes
 import os
+import re
 import subprocess
 from fractions import Fraction
 
@@ -167,6 +168,17 @@ def test_the_new_kernels_use_no_scratch_and_the_search_keeps_its_occupancy():
     assert [lds // (k * 256 * 8) for k in (20, 30, 62)] == [4, 2, 1]
     assert mine["grid_scan_kernel"]["lds"] == 16 and mine["grid_bounds_kernel"]["lds"] == 96
     assert mine["grid_count_kernel"]["lds"] == mine["grid_scatter_kernel"]["lds"] == mine["grid_clear_kernel"]["lds"] == 0
+
+
+def test_the_ring_walk_is_written_once():
+    """Every search on the grid walks grid_walk.h's rings: among the kernel sources and their headers the enumeration -- rmax, the
+    shell test -- and the faces of the ring bound stand in that header alone, and the four searches include it."""
+    csrc = os.path.join(ROOT, "vcr-net_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    assert [f for f, t in text.items() if re.search(r"\b(rmax|shell)\b", t)] == ["grid_walk.h"]
+    assert [f for f, t in text.items() if "gd_face(" in t] == ["grid_build.h", "grid_walk.h"]      # (the faces decide the cells too)
+    for f in ("grid.hip", "gridnn.hip", "radius.hip", "query.hip"):
+        assert '#include "grid_walk.h"' in text[f], f
 
 
 # ------------------------------------------------------------------------------------------------------------- the restatement

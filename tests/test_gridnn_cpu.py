@@ -232,6 +232,9 @@ def test_the_new_kernels_use_no_scratch_and_the_search_keeps_eight_waves():
     text = open(os.path.join(ROOT, "vcr-net_amd", "csrc", "gridnn.hip")).read()
     kernel = text[text.index("void grid_nn_kernel"):text.index("}  // namespace")]
     assert "atomic" not in kernel and "__syncthreads" not in kernel and "__shared__" not in kernel
+    assert "gd_walk(" in kernel                              # ... nor has the walk it runs
+    walk = open(os.path.join(ROOT, "vcr-net_amd", "csrc", "grid_walk.h")).read()
+    assert "atomic" not in walk and "__syncthreads" not in walk and "__shared__" not in walk
     for k in ("grid_bounds_kernel", "grid_clear_kernel", "grid_count_kernel", "grid_scan_kernel", "grid_scatter_kernel"):
         assert short[k]["file"] == "grid.hip" and short[k].get("scratch", 0) == 0
 

@@ -24,8 +24,8 @@ HEADER = os.path.join(INCLUDE, "query", "vcr_hip_query.h")
 EINVAL, EWORKSPACE, EUNSUPPORTED = -1, -2, -3
 ENTRY_POINTS = {"vcr_query_knn_f32", "vcr_query_knn_workspace_bytes", "vcr_query_knn_form",
                 "vcr_query_radius_f32", "vcr_query_radius_workspace_bytes", "vcr_query_radius_form"}
-KERNELS = {"query_knn_kernel", "query_count_kernel", "query_offsets_kernel", "query_fill_kernel", "query_order_kernel",
-           "query_pad_kernel"}
+KERNELS = {"query_knn_kernel", "query_count_kernel", "rows_offsets_kernel", "query_fill_kernel", "rows_order_kernel",
+           "rows_pad_kernel"}
 N, M, K = 300, 200, 20
 
 
@@ -302,9 +302,10 @@ def test_the_forms_and_workspaces_are_host_only_and_follow_the_header(lib):
 
 
 def test_the_kernels_of_query_hip_use_no_scratch_and_keep_eight_waves():
-    """hipcc's remarks for query.hip.  Its own kernel set is the six query_* kernels: the build kernels are grid.hip's text
-    (grid_build.h), and the remarks list a kernel under the first file that compiles it.  No scratch, no VGPR or SGPR spill; the
-    kNN kernel's rows are dynamic LDS (k x 256 keys), the ordering stages VCR_QUERY_CHUNK keys."""
+    """hipcc's remarks for query.hip.  Its kernel set is the three query_* kernels and the row tail (csr_rows.h's text, which
+    radius.hip compiles too): the build kernels are grid.hip's text (grid_build.h), and the remarks list a kernel under the first
+    file that compiles it.  No scratch, no VGPR or SGPR spill; the kNN kernel's rows are dynamic LDS (k x 256 keys), the
+    ordering stages VCR_QUERY_CHUNK keys."""
     import vcrnet_amd  # noqa: F401
     from vcrnet_amd import build, query
     build.build()
@@ -319,11 +320,11 @@ def test_the_kernels_of_query_hip_use_no_scratch_and_keep_eight_waves():
         assert v.get("scratch", 0) == 0 and v.get("vgpr_spill", 0) == 0 and v.get("sgpr_spill", 0) == 0, (d, v)
         assert v["occupancy"] == 8 and v["vgprs"] <= 64 and v["agprs"] == 0, (d, v)
     assert {d: v["lds"] for d, v in mine.items()} == {
-        "query_knn_kernel": 0, "query_count_kernel": 0, "query_offsets_kernel": 32, "query_fill_kernel": 0,
-        "query_order_kernel": query.CHUNK * 8, "query_pad_kernel": 0}
+        "query_knn_kernel": 0, "query_count_kernel": 0, "rows_offsets_kernel": 32, "query_fill_kernel": 0,
+        "rows_order_kernel": query.CHUNK * 8, "rows_pad_kernel": 0}
     # what query.hip shares keeps its owner
     assert by_name["grid_scatter_kernel"]["file"] == by_name["grid_count_kernel"]["file"] == "grid.hip"
-    assert by_name["radius_order_kernel"]["file"] == "radius.hip" and by_name["grid_search_kernel"]["file"] == "grid.hip"
+    assert by_name["radius_order_lane_kernel"]["file"] == "radius.hip" and by_name["grid_search_kernel"]["file"] == "grid.hip"
 
 
 # ------------------------------------------------------------------------------------------------------------ the Python layer

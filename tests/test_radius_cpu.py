@@ -25,8 +25,8 @@ OTHERS = ("vcr_hip.h", "vcr_hip_score.h", "vcr_hip_refine.h", "vcr_hip_plane.h",
 EINVAL, EWORKSPACE, EUNSUPPORTED = -1, -2, -3
 ENTRY_POINTS = {"vcr_grid_radius_f32", "vcr_grid_radius_workspace_bytes", "vcr_grid_radius_form",
                 "vcr_outlier_radius_grid_f32", "vcr_outlier_radius_grid_workspace_bytes", "vcr_outlier_radius_grid_form"}
-KERNELS = {"radius_count_kernel", "radius_offsets_kernel", "radius_fill_kernel", "radius_order_kernel", "radius_order_lane_kernel",
-           "radius_pad_kernel"}
+KERNELS = {"radius_count_kernel", "radius_fill_kernel", "radius_order_lane_kernel"}
+ROW_KERNELS = {"rows_offsets_kernel", "rows_order_kernel", "rows_pad_kernel"}      # csr_rows.h's, shared with query.hip
 INSIDE = (2, 12, 70)
 
 
@@ -304,16 +304,16 @@ def test_the_filters_sibling_returns_its_argument_errors_and_its_workspace_witho
 
 
 def test_the_kernels_of_radius_hip_use_no_scratch_and_keep_eight_waves():
-    """hipcc's remarks for radius.hip.  Its own kernel set is the six radius_* kernels: the five build kernels are grid.hip's text
-    (grid_build.h), the filter's tail outlier.hip's (outlier_tail.h), and the remarks list a kernel under the first file that
-    compiles it.  No scratch, no VGPR or SGPR spill.  As recorded from the build (waves a SIMD, static LDS bytes a workgroup; none
-    takes dynamic LDS):
+    """hipcc's remarks for the six kernels radius.hip runs behind the grid.  Its own set is the three radius_* kernels: the row
+    tail is csr_rows.h's text, shared with query.hip, the five build kernels are grid.hip's (grid_build.h), the filter's tail
+    outlier.hip's (outlier_tail.h), and the remarks list a kernel under the first file that compiles it.  No scratch, no VGPR or
+    SGPR spill.  As recorded from the build (waves a SIMD, static LDS bytes a workgroup; none takes dynamic LDS):
       radius_count_kernel       8 waves,    0 B   (50 VGPRs)
-      radius_offsets_kernel     8 waves,   32 B   (the four waves' 64-bit totals)
-      radius_fill_kernel        8 waves,    0 B   (42 VGPRs)
-      radius_order_kernel       8 waves, 1024 B   (VCR_RADIUS_CHUNK = 128 keys of 8 bytes; a workgroup is ONE wave)
+      rows_offsets_kernel       8 waves,   32 B   (the four waves' 64-bit totals)
+      radius_fill_kernel        8 waves,    0 B   (39 VGPRs)
+      rows_order_kernel         8 waves, 1024 B   (VCR_RADIUS_CHUNK = 128 keys of 8 bytes; a workgroup is ONE wave)
       radius_order_lane_kernel  8 waves,    0 B
-      radius_pad_kernel         8 waves,    0 B"""
+      rows_pad_kernel           8 waves,    0 B"""
     import vcrnet_amd  # noqa: F401
     from vcrnet_amd import build, radius
     build.build()
@@ -323,13 +323,15 @@ def test_the_kernels_of_radius_hip_use_no_scratch_and_keep_eight_waves():
     by_name = {d.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]: res[n] for n, d in zip(names, dem)}
     mine = {d: v for d, v in by_name.items() if v["file"] == "radius.hip"}
     assert set(mine) == KERNELS
+    assert all(by_name[d]["file"] == "query.hip" for d in ROW_KERNELS)
+    mine.update({d: by_name[d] for d in ROW_KERNELS})
     for d, v in mine.items():
         print(d, v)
         assert v.get("scratch", 0) == 0 and v.get("vgpr_spill", 0) == 0 and v.get("sgpr_spill", 0) == 0, (d, v)
         assert v["occupancy"] == 8 and v["vgprs"] <= 64 and v["agprs"] == 0, (d, v)
     assert {d: v["lds"] for d, v in mine.items()} == {
-        "radius_count_kernel": 0, "radius_offsets_kernel": 32, "radius_fill_kernel": 0, "radius_order_kernel": radius.CHUNK * 8,
-        "radius_order_lane_kernel": 0, "radius_pad_kernel": 0}
+        "radius_count_kernel": 0, "rows_offsets_kernel": 32, "radius_fill_kernel": 0, "rows_order_kernel": radius.CHUNK * 8,
+        "radius_order_lane_kernel": 0, "rows_pad_kernel": 0}
     # what radius.hip shares keeps its owner and its resources
     assert by_name["grid_scatter_kernel"]["file"] == "grid.hip" and by_name["outlier_write_kernel"]["file"] == "outlier.hip"
     assert by_name["outlier_mark_kernel"]["file"] == by_name["outlier_offsets_kernel"]["file"] == "outlier.hip"

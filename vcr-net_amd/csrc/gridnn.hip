@@ -9,15 +9,15 @@
 // Every search (gridnn_search):
 //   grid_nn_kernel   one lane per source point (lane s of the launch takes point perm[s], or s in index order), moved by the
 //                    pose in registers (the scan's expression).  The best key (d2's bits) << 32 | j lives in a register pair.
-//                    Rings of cells around the query's cell -- the query clamped into the grid per axis --, section 4.19's
-//                    enumeration: one run a (y, z) row of the shell, two end cells inside it.  After ring r the bound is the
+//                    Rings of cells around the query's cell -- the query clamped into the grid per axis --: grid_walk.h's
+//                    gd_walk, section 4.19's enumeration and ring bound with the d * d term.  After ring r the bound is the
 //                    larger of the ring bound and the OUTSIDE bound (the query's distance to the target's box, per axis one
 //                    subtraction); the walk stops when the best d2 is strictly below it, when it is strictly above the cap
 //                    (or +inf: nothing behind it is a candidate), or when the grid is exhausted.  A query whose outside bound
 //                    exceeds the cap, or that is not finite, walks nothing.  A best beyond the cap is written as (-1, +inf).
 // No scratch, no atomics in the search, no waits between workgroups; every loop is bounded by Nt or the cells per axis, and
 // every run of candidates is clamped to [0, Nt).
-#include "grid_build.h"
+#include "grid_walk.h"
 #include "grid_nn.h"
 
 namespace {
@@ -90,42 +90,18 @@ __global__ __launch_bounds__(GD_BLOCK) void grid_nn_kernel(GnSearch p) {
     if (out <= cap2 && out < inf) {
       const float4* __restrict__ sorted = p.sorted + (size_t)b * Nt;
       const int* __restrict__ start = p.counter + (size_t)b * p.gstride; // cell c: sorted[start[c] ... start[c + 1])
-      const int nx = g.n[0], ny = g.n[1], nz = g.n[2];
-      const int cx = gd_cell(px, g.lo[0], g.h, g.inv, nx);               // clamped into the grid: below lo cell 0, above n - 1
-      const int cy = gd_cell(py, g.lo[1], g.h, g.inv, ny);
-      const int cz = gd_cell(pz, g.lo[2], g.h, g.inv, nz);
-      int rmax = cx > nx - 1 - cx ? cx : nx - 1 - cx;
-      rmax = cy > rmax ? cy : rmax; rmax = ny - 1 - cy > rmax ? ny - 1 - cy : rmax;
-      rmax = cz > rmax ? cz : rmax; rmax = nz - 1 - cz > rmax ? nz - 1 - cz : rmax;
-      const int q[3] = {cx, cy, cz};
-      for (int r = 0; r <= rmax; ++r) {                    // (bounded by the cells per axis)
-        const int z0 = cz - r > 0 ? cz - r : 0, z1 = cz + r < nz - 1 ? cz + r : nz - 1;
-        const int y0 = cy - r > 0 ? cy - r : 0, y1 = cy + r < ny - 1 ? cy + r : ny - 1;
-        const int x0 = cx - r > 0 ? cx - r : 0, x1 = cx + r < nx - 1 ? cx + r : nx - 1;
-        for (int zz = z0; zz <= z1; ++zz)
-          for (int yy = y0; yy <= y1; ++yy) {
-            const int row = (zz * ny + yy) * nx;
-            const bool shell = zz - cz == r || cz - zz == r || yy - cy == r || cy - yy == r;
-            if (shell) {                                   // the whole x range of the ring: one run
-              gn_run(sorted, start[row + x0], start[row + x1 + 1], Nt, px, py, pz, best);
-            } else {                                       // its two end cells
-              if (cx - r >= 0) gn_run(sorted, start[row + cx - r], start[row + cx - r + 1], Nt, px, py, pz, best);
-              if (cx + r <= nx - 1) gn_run(sorted, start[row + cx + r], start[row + cx + r + 1], Nt, px, py, pz, best);
-            }
-          }
-        // what no point behind ring r can undercut: section 4.19's ring bound (a side that exists has g >= 0, for a clamped
-        // query too), and never less than the outside bound
-        float bound = inf;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          if (q[c] + r + 1 <= g.n[c] - 1) { const float d = gd_face(q[c] + r + 1, g.h, g.lo[c]) - xq[c]; bound = fminf(bound, d * d); }
-          if (q[c] - r >= 1) { const float d = xq[c] - gd_face(q[c] - r, g.h, g.lo[c]); bound = fminf(bound, d * d); }
-        }
+      const int cx = gd_cell(px, g.lo[0], g.h, g.inv, g.n[0]);           // clamped into the grid: below lo cell 0, above n - 1
+      const int cy = gd_cell(py, g.lo[1], g.h, g.inv, g.n[1]);
+      const int cz = gd_cell(pz, g.lo[2], g.h, g.inv, g.n[2]);
+      auto run = [&](int a0, int a1) { gn_run(sorted, a0, a1, Nt, px, py, pz, best); };
+      // What no point behind ring r can undercut is never less than the outside bound.  The walk stops STRICTLY below the bound:
+      // a tie behind the ring with a lower index could still win.  STRICTLY above the cap: nothing unseen is an inlier.  +inf: no
+      // side is left (the grid is exhausted), or nothing behind it is a candidate
+      auto stop = [&](float bound) {
         bound = fmaxf(bound, out);
-        // STRICTLY below the bound: a tie behind the ring with a lower index could still win.  STRICTLY above the cap: nothing
-        // unseen is an inlier.  +inf: no side is left (the grid is exhausted), or nothing behind it is a candidate
-        if (__uint_as_float((uint32_t)(best >> 32)) < bound || bound > cap2 || bound == inf) break;
-      }
+        return __uint_as_float((uint32_t)(best >> 32)) < bound || bound > cap2 || bound == inf;
+      };
+      gd_walk(g, start, cx, cy, cz, xq, GdSquare{}, run, stop);
     }
   }
   const float d2 = __uint_as_float((uint32_t)(best >> 32));
@@ -152,7 +128,7 @@ int gridnn_plan(const vcr_grid_nn_args* user, int family, int searches, int B, i
   *p = GridNnPlan{};
   vcr_grid_nn_args g;
   if (vcr_take_args(user, &g, sizeof(vcr_grid_nn_args))) return VCR_EINVAL;
-  if (!(g.cell >= 0.f) || g.cell == __builtin_huge_valf()) return VCR_EINVAL;           // negative, NaN, +inf
+  if (!gd_cell_ok(g.cell)) return VCR_EINVAL;
   if (g.order < 0 || g.order > 2) return VCR_EINVAL;
   p->B = B; p->Ns = Ns; p->Nt = Nt;
   p->cell = g.cell;

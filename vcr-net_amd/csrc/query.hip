@@ -12,24 +12,19 @@
 //                         (d2's bits) << 32 | j, as in grid.hip; a slot without a neighbour holds (+inf, -1)
 // vcr_query_radius_f32: radius.hip's sequence over the M rows
 //   query_count_kernel    one lane per query: the walk, n_i to count[b, i]
-//   query_offsets_kernel  one workgroup per cloud: the 64-bit exclusive scan of the counts (wg_offsets64) to row_start, total
+//   rows_offsets_kernel   csr_rows.h's tail, shared with radius.hip: the 64-bit scan of the counts to row_start, total
 //   query_fill_kernel     the same walk: lane i appends its hits' keys to its private segment of the scratch row; no atomics
-//   query_order_kernel    a wave per row: a rank sort out of the scratch through LDS in chunks of VCR_QUERY_CHUNK (a row's keys
-//                         are distinct, so rank(e) = #{keys < key_e} is a permutation)
-//   query_pad_kernel      -1 / +inf behind total[b], and over the clouds that do not fit
-// The ring enumeration is written once here, qy_walk, for the three kernels that walk (it restates grid.hip's and radius.hip's
-// with the query's cell clamped, no index excluded and the bound joined with the query's distances to the box; those two files
-// are unchanged).  No scratch memory, no waits between
-// workgroups; every loop is bounded by N, M, k, a row's length or the cells per axis; every run of candidates is clamped to
-// [0, N), every write to its row.
-#include "grid_build.h"
-#include "../../include/query/vcr_hip_query.h"
+//   rows_order_kernel     a wave per row: csr_rows.h's rank sort out of the scratch through LDS in chunks of VCR_QUERY_CHUNK
+//   rows_pad_kernel       -1 / +inf behind total[b], and over the clouds that do not fit
+// The walk is grid_walk.h's, with the query's cell clamped and each side's term joined with the query's distances to the box
+// (QySide); qy_walk puts the three kernels' common early-outs in front of it.  No scratch memory, no waits between workgroups;
+// every loop is bounded by N, M, k, a row's length or the cells per axis; every run of candidates is clamped to [0, N), every
+// write to its row.
+#include "grid_walk.h"
+#include "csr_rows.h"
 
 namespace {
 
-constexpr int QY_CHUNK = VCR_QUERY_CHUNK;
-constexpr int QY_WAVE = 64;
-static_assert(QY_CHUNK % QY_WAVE == 0, "a wave stages a chunk in whole passes");
 static_assert(VCR_QUERY_MAX_N == VCR_GRID_MAX_N && VCR_QUERY_MAX_K == VCR_GRID_MAX_K, "the points' grid is grid_build.h's");
 
 // what the walking kernels share: the points' grid and the queries, in index order (qsorted == NULL) or in cell order
@@ -68,67 +63,29 @@ __device__ __forceinline__ float qy_outside(const GdGrid& g, const float xq[3], 
   return out;
 }
 
-// What no point behind the side at distance d along axis c can undercut: its difference along c is at least max(d, o_c) and
+// What no point behind the side at distance d along axis C can undercut: its difference along C is at least max(d, o_C) and
 // along the other axes at least o_a, and d2's expression is monotone in each of them (every rounding is).  Inside the box
 // (o = 0) this is d * d, section 4.19's term, bit for bit
-template <int C>
-__device__ __forceinline__ float qy_side(const float o[3], float d) {
-  const float mx = C == 0 ? fmaxf(d, o[0]) : o[0], my = C == 1 ? fmaxf(d, o[1]) : o[1], mz = C == 2 ? fmaxf(d, o[2]) : o[2];
-  return fmaf(mz, mz, fmaf(my, my, mx * mx));
-}
+struct QySide {
+  const float* o;
+  template <int C>
+  __device__ __forceinline__ float term(float d) const {
+    const float mx = C == 0 ? fmaxf(d, o[0]) : o[0], my = C == 1 ? fmaxf(d, o[1]) : o[1], mz = C == 2 ? fmaxf(d, o[2]) : o[2];
+    return fmaf(mz, mz, fmaf(my, my, mx * mx));
+  }
+};
 
-template <int C>
-__device__ __forceinline__ float qy_axis_bound(const GdGrid& g, const float xq[3], const float o[3], int qc, int r, float bound) {
-  if (qc + r + 1 <= g.n[C] - 1) bound = fminf(bound, qy_side<C>(o, gd_face(qc + r + 1, g.h, g.lo[C]) - xq[C]));
-  if (qc - r >= 1) bound = fminf(bound, qy_side<C>(o, xq[C] - gd_face(qc - r, g.h, g.lo[C])));
-  return bound;
-}
-
-// The rings around the query's CLAMPED cell (below lo cell 0, above the last face n - 1): section 4.19's enumeration -- one run
-// a (y, z) row of the shell, two end cells inside it -- and its ring bound, which holds for a clamped cell too (a side that
-// exists has a distance >= 0; one that does not contributes nothing), each side's term joined with the query's distances o to
-// the box (qy_side).  run(a0, a1) looks at sorted[a0 ... a1); stop(bound) ends the walk after a ring.  Nothing is walked in a
-// cloud without a finite point (start[cells], the end of its last cell, is the number of its finite points).
+// The rings around the query's CLAMPED cell (below lo cell 0, above the last face n - 1), each side's term joined with the
+// query's distances o to the box.  Nothing is walked in a cloud without a finite point (start[cells], the end of its last cell,
+// is the number of its finite points).
 template <class Run, class Stop>
 __device__ __forceinline__ void qy_walk(const GdGrid& g, const int* __restrict__ start, const float xq[3], const float o[3],
                                         Run& run, Stop& stop) {
-  const int nx = g.n[0], ny = g.n[1], nz = g.n[2];
   if (g.cells < 1 || start[g.cells] <= 0) return;
-  const int cx = gd_cell(xq[0], g.lo[0], g.h, g.inv, nx);
-  const int cy = gd_cell(xq[1], g.lo[1], g.h, g.inv, ny);
-  const int cz = gd_cell(xq[2], g.lo[2], g.h, g.inv, nz);
-  int rmax = cx > nx - 1 - cx ? cx : nx - 1 - cx;
-  rmax = cy > rmax ? cy : rmax; rmax = ny - 1 - cy > rmax ? ny - 1 - cy : rmax;
-  rmax = cz > rmax ? cz : rmax; rmax = nz - 1 - cz > rmax ? nz - 1 - cz : rmax;
-  for (int r = 0; r <= rmax; ++r) {                        // (bounded by the cells per axis)
-    const int z0 = cz - r > 0 ? cz - r : 0, z1 = cz + r < nz - 1 ? cz + r : nz - 1;
-    const int y0 = cy - r > 0 ? cy - r : 0, y1 = cy + r < ny - 1 ? cy + r : ny - 1;
-    const int x0 = cx - r > 0 ? cx - r : 0, x1 = cx + r < nx - 1 ? cx + r : nx - 1;
-    for (int z = z0; z <= z1; ++z)
-      for (int y = y0; y <= y1; ++y) {
-        const int row = (z * ny + y) * nx;
-        const bool shell = z - cz == r || cz - z == r || y - cy == r || cy - y == r;
-        if (shell) {                                       // the whole x range of the ring: one run
-          run(start[row + x0], start[row + x1 + 1]);
-        } else {                                           // its two end cells
-          if (cx - r >= 0) run(start[row + cx - r], start[row + cx - r + 1]);
-          if (cx + r <= nx - 1) run(start[row + cx + r], start[row + cx + r + 1]);
-        }
-      }
-    // what no point behind ring r can undercut: per side that exists one subtraction, the smallest of the sides' terms
-    float bound = __builtin_huge_valf();
-    bound = qy_axis_bound<0>(g, xq, o, cx, r, bound);
-    bound = qy_axis_bound<1>(g, xq, o, cy, r, bound);
-    bound = qy_axis_bound<2>(g, xq, o, cz, r, bound);
-    if (stop(bound)) break;
-  }
-}
-
-// the key of candidate sorted[s] against the query: (d2's bits) << 32 | j, d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) of x_j - q
-__device__ __forceinline__ u64 qy_key(const float4 c, const float xq[3]) {
-  const float dx = c.x - xq[0], dy = c.y - xq[1], dz = c.z - xq[2];
-  const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-  return (u64)__float_as_uint(d2) << 32 | (uint32_t)__float_as_int(c.w);
+  const int cx = gd_cell(xq[0], g.lo[0], g.h, g.inv, g.n[0]);
+  const int cy = gd_cell(xq[1], g.lo[1], g.h, g.inv, g.n[1]);
+  const int cz = gd_cell(xq[2], g.lo[2], g.h, g.inv, g.n[2]);
+  gd_walk(g, start, cx, cy, cz, xq, QySide{o}, run, stop);
 }
 
 // ---- the k nearest
@@ -152,31 +109,19 @@ __global__ __launch_bounds__(GD_BLOCK) void query_knn_kernel(QyKnn p) {
     auto run = [&](int a0, int a1) {
       a0 = a0 > 0 ? a0 : 0;
       a1 = a1 < N ? a1 : N;
-      for (int c = a0; c < a1; ++c) {
-        const u64 key = qy_key(sorted[c], q.x);
-        if ((uint32_t)(key >> 32) < GD_INF && key < kth) { // (a NaN's bits are above +inf's; kth <= none)
-          int at = k - 1;
-          for (; at > 0; --at) {                           // (bounded by k)
-            const u64 prev = lk[(at - 1) * GD_BLOCK];
-            if (prev < key) break;
-            lk[at * GD_BLOCK] = prev;
-          }
-          lk[at * GD_BLOCK] = key;
-          kth = lk[(k - 1) * GD_BLOCK];
-        }
-      }
+      for (int c = a0; c < a1; ++c) gd_insert(lk, k, gd_key(sorted[c], q.x), kth);       // (kth <= none)
     };
     // STRICTLY below: a tie behind the ring could still enter
-    auto stop = [&](float bound) { return __uint_as_float((uint32_t)(kth >> 32)) < bound; };
+    auto stop = [&](float bound) { return gd_key_d2(kth) < bound; };
     float o[3];
     // (an outside bound of +inf: every d2 overflows, nothing is a candidate)
     if (qy_outside(g, q.x, o) < __builtin_huge_valf()) qy_walk(g, p.w.counter + (size_t)b * p.w.gstride, q.x, o, run, stop);
   }
   int* __restrict__ oi = p.idx + ((size_t)b * M + q.i) * k;
-  for (int a = 0; a < k; ++a) oi[a] = (int)(uint32_t)lk[a * GD_BLOCK];
+  for (int a = 0; a < k; ++a) oi[a] = gd_key_j(lk[a * GD_BLOCK]);
   if (p.d2) {
     float* __restrict__ od = p.d2 + ((size_t)b * M + q.i) * k;
-    for (int a = 0; a < k; ++a) od[a] = __uint_as_float((uint32_t)(lk[a * GD_BLOCK] >> 32));
+    for (int a = 0; a < k; ++a) od[a] = gd_key_d2(lk[a * GD_BLOCK]);
   }
 }
 
@@ -197,8 +142,8 @@ __device__ __forceinline__ void qy_radius_walk(const QyWalk& p, int b, const QyQ
     a0 = a0 > 0 ? a0 : 0;
     a1 = a1 < N ? a1 : N;
     for (int c = a0; c < a1; ++c) {
-      const u64 key = qy_key(sorted[c], q.x);
-      if (__uint_as_float((uint32_t)(key >> 32)) <= r2) hit(key);
+      const u64 key = gd_key(sorted[c], q.x);
+      if (gd_key_d2(key) <= r2) hit(key);
     }
   };
   // STRICTLY above: an unseen point at exactly r2 is a hit (the bound is never below out: every side's term holds every o_c)
@@ -219,14 +164,6 @@ __global__ __launch_bounds__(GD_BLOCK) void query_count_kernel(QyCount p) {
   p.count[(size_t)b * p.w.M + q.i] = n;
 }
 
-__global__ __launch_bounds__(GD_BLOCK) void query_offsets_kernel(const int* count, long long* row_start, long long* total, int M) {
-  __shared__ long long wtot[WG_WAVES];
-  const int b = blockIdx.x;
-  long long* rs = row_start + (size_t)b * ((size_t)M + 1);
-  const long long all = wg_offsets64(count + (size_t)b * M, rs, M, wtot);
-  if (threadIdx.x == 0) { rs[M] = all; total[b] = all; }
-}
-
 // row_start [B][M + 1]; scratch [B][capacity]: a cloud's unordered keys, row i at row_start[b, i]
 struct QyFill { QyWalk w; float r2; const long long* row_start; int capacity; u64* scratch; };
 
@@ -236,60 +173,13 @@ __global__ __launch_bounds__(GD_BLOCK) void query_fill_kernel(QyFill p) {
   const long long* __restrict__ rs = p.row_start + (size_t)b * ((size_t)M + 1);
   if (s >= M || rs[M] > (long long)p.capacity) return;     // (no barrier below; a cloud that does not fit: the pad writes it)
   const QyQuery q = qy_query(p.w, b, s);
-  const long long at = rs[q.i];
-  const long long len = rs[q.i + 1] - at, left = (long long)p.capacity - at;
-  const long long room = len < left ? len : left;          // the lane's segment, clamped to the row and to the cloud's slots
-  if (at < 0 || room <= 0) return;
-  u64* __restrict__ row = p.scratch + (size_t)b * p.capacity + (size_t)at;
+  const RowsSeg sg = rows_segment(rs, q.i, p.capacity);    // the lane's segment
+  const long long room = sg.len;
+  if (sg.at < 0 || room <= 0) return;
+  u64* __restrict__ row = p.scratch + (size_t)b * p.capacity + (size_t)sg.at;
   long long w = 0;
   auto hit = [&](u64 key) { if (w < room) row[w] = key; ++w; };
   qy_radius_walk(p.w, b, q, p.r2, hit);
-}
-
-struct QyOrder { const long long* row_start; const u64* scratch; int M, capacity; int* idx; float* d2; };
-
-// One workgroup of ONE wave per row: 64 elements are ranked a pass against the whole row, which passes through LDS in chunks
-__global__ __launch_bounds__(QY_WAVE) void query_order_kernel(QyOrder p) {
-  __shared__ u64 keys[QY_CHUNK];
-  const int lane = threadIdx.x, M = p.M;
-  const int b = (int)(blockIdx.x / (unsigned)M), i = (int)(blockIdx.x % (unsigned)M);
-  const long long* __restrict__ rs = p.row_start + (size_t)b * ((size_t)M + 1);
-  if (rs[M] > (long long)p.capacity) return;               // (workgroup-uniform)
-  const long long at = rs[i];
-  long long len = rs[i + 1] - at;
-  len = len < (long long)p.capacity - at ? len : (long long)p.capacity - at;
-  if (at < 0 || len <= 0) return;                          // (workgroup-uniform)
-  const int n = (int)len;                                  // <= N
-  const size_t base = (size_t)b * p.capacity + (size_t)at;
-  const u64* __restrict__ row = p.scratch + base;
-  for (int e0 = 0; e0 < n; e0 += QY_WAVE) {                // (workgroup-uniform: bounded by the row's length)
-    const int e = e0 + lane;
-    const u64 key = e < n ? row[e] : ~0ull;
-    int rank = 0;
-    for (int c0 = 0; c0 < n; c0 += QY_CHUNK) {
-      const int m = n - c0 < QY_CHUNK ? n - c0 : QY_CHUNK;
-      __syncthreads();                                     // the previous chunk has been read
-      for (int f = lane; f < m; f += QY_WAVE) keys[f] = row[c0 + f];
-      __syncthreads();
-      for (int f = 0; f < m; ++f) rank += keys[f] < key ? 1 : 0;         // one address for every lane: broadcast reads
-    }
-    if (e < n && rank < n) {                               // (rank < n always: the keys are distinct)
-      p.idx[base + rank] = (int)(uint32_t)key;
-      if (p.d2) p.d2[base + rank] = __uint_as_float((uint32_t)(key >> 32));
-    }
-  }
-}
-
-__global__ __launch_bounds__(GD_BLOCK) void query_pad_kernel(const long long* row_start, int M, int capacity, int per_cloud,
-                                                             int* idx, float* d2) {
-  const int b = (int)(blockIdx.x / (unsigned)per_cloud), blk = (int)(blockIdx.x % (unsigned)per_cloud);
-  const long long all = row_start[(size_t)b * ((size_t)M + 1) + M];
-  const int from = all >= 0 && all <= (long long)capacity ? (int)all : 0;           // a cloud that does not fit: every slot
-  const size_t base = (size_t)b * capacity;
-  for (long long s = (long long)from + blk * GD_BLOCK + (int)threadIdx.x; s < capacity; s += (long long)per_cloud * GD_BLOCK) {
-    idx[base + s] = -1;
-    if (d2) d2[base + s] = __builtin_huge_valf();
-  }
 }
 
 // How one call runs: the points' grid | the queries' cells, counters and cell order | (radius) the unordered keys
@@ -357,13 +247,11 @@ static int qy_build(const float* xyz, const float* queries, int B, int N, int M,
   return VCR_LAUNCH_RC();
 }
 
-static bool qy_cell_ok(float cell) { return cell >= 0.f && cell != __builtin_huge_valf(); }          // not negative, NaN, +inf
-
 // ---- vcr_query_knn_*
 
 static int qy_knn_plan(const vcr_query_knn_args* ua, vcr_query_knn_args* a, QyLayout* l) {
   if (vcr_take_args(ua, a, offsetof(vcr_query_knn_args, d2))) return VCR_EINVAL;
-  if (!a->xyz || !a->queries || !a->idx || a->B < 1 || !qy_cell_ok(a->cell)) return VCR_EINVAL;
+  if (!a->xyz || !a->queries || !a->idx || a->B < 1 || !gd_cell_ok(a->cell)) return VCR_EINVAL;
   const int e = qy_layout(a->B, a->N, a->M, 0, a->variant, a->k, l);
   if (e) return e;
   return a->k < 1 || a->k > VCR_QUERY_MAX_K ? VCR_EUNSUPPORTED : VCR_OK;
@@ -407,9 +295,7 @@ extern "C" int vcr_query_knn_f32(const vcr_query_knn_args* ua, void* workspace, 
 static int qy_radius_plan(const vcr_query_radius_args* ua, vcr_query_radius_args* a, QyLayout* l, float* r2) {
   if (vcr_take_args(ua, a, offsetof(vcr_query_radius_args, idx))) return VCR_EINVAL;
   if (!a->xyz || !a->queries || !a->count || !a->row_start || !a->total || a->B < 1) return VCR_EINVAL;
-  if (!(a->radius > 0.f) || a->radius == __builtin_huge_valf()) return VCR_EINVAL;                  // <= 0, NaN, +inf
-  *r2 = a->radius * a->radius;                             // fp32, one rounding
-  if (!(*r2 < __builtin_huge_valf()) || !qy_cell_ok(a->cell)) return VCR_EINVAL;
+  if (!gd_radius_ok(a->radius, r2) || !gd_cell_ok(a->cell)) return VCR_EINVAL;
   if (a->capacity < 0 || (!a->idx && a->capacity != 0) || (a->d2 && !a->idx)) return VCR_EINVAL;
   return qy_layout(a->B, a->N, a->M, a->capacity, a->variant, 0, l);
 }
@@ -447,21 +333,14 @@ extern "C" int vcr_query_radius_f32(const vcr_query_radius_args* ua, void* works
   unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
   QyWalk wk;
   if ((e = qy_build(a.xyz, a.queries, a.B, a.N, a.M, a.cell > 0.f ? a.cell : a.radius, l, w, s, &wk))) return e;
-  const dim3 block(GD_BLOCK), clouds((unsigned)a.B), lanes((unsigned)((long)a.B * l.nblk_q));
+  const dim3 block(GD_BLOCK), lanes((unsigned)((long)a.B * l.nblk_q));
   long long* row_start = reinterpret_cast<long long*>(a.row_start);
   hipLaunchKernelGGL(query_count_kernel, lanes, block, 0, s, QyCount{wk, r2, a.count});
   if ((e = VCR_LAUNCH_RC())) return e;
-  hipLaunchKernelGGL(query_offsets_kernel, clouds, block, 0, s, a.count, row_start, reinterpret_cast<long long*>(a.total), a.M);
-  if ((e = VCR_LAUNCH_RC())) return e;
+  if ((e = rows_offsets(a.count, row_start, reinterpret_cast<long long*>(a.total), a.B, a.M, s))) return e;
   if (!a.idx || a.capacity == 0) return VCR_OK;
   u64* scratch = reinterpret_cast<u64*>(w + l.scratch_off);
   hipLaunchKernelGGL(query_fill_kernel, lanes, block, 0, s, QyFill{wk, r2, row_start, a.capacity, scratch});
   if ((e = VCR_LAUNCH_RC())) return e;
-  hipLaunchKernelGGL(query_order_kernel, dim3((unsigned)((long)a.B * a.M)), dim3(QY_WAVE), 0, s,
-                     QyOrder{row_start, scratch, a.M, a.capacity, a.idx, a.d2});
-  if ((e = VCR_LAUNCH_RC())) return e;
-  const int pad_x = (a.capacity + GD_BLOCK - 1) / GD_BLOCK < 256 ? (a.capacity + GD_BLOCK - 1) / GD_BLOCK : 256;
-  hipLaunchKernelGGL(query_pad_kernel, dim3((unsigned)((long)a.B * pad_x)), block, 0, s, row_start, a.M, a.capacity, pad_x,
-                     a.idx, a.d2);
-  return VCR_LAUNCH_RC();
+  return rows_order_pad(RowsOrder{row_start, scratch, a.M, a.capacity, a.idx, a.d2}, a.B, s);
 }
