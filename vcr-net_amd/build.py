@@ -29,6 +29,8 @@ SEGMENT_HEADERS = [os.path.join(INCLUDE, "segment", f) for f in ("vcr_hip_segmen
 ORIENT_HEADERS = [os.path.join(INCLUDE, "orient", f) for f in ("vcr_hip_orient.h",)]   # (... and include/segment/'s)
 ISS_HEADERS = [os.path.join(INCLUDE, "keypoint", f) for f in ("vcr_hip_iss.h",)]   # (... and include/orient/'s)
 QUERY_HEADERS = [os.path.join(INCLUDE, "query", f) for f in ("vcr_hip_query.h",)]   # (... and include/keypoint/'s)
+# (... and include/query/'s; tests hold query.o's digest to the lists above, so this one enters the digest of support.o ALONE)
+SUPPORT_HEADERS = [os.path.join(INCLUDE, "support", f) for f in ("vcr_hip_support.h",)]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off"]   # no silent a*b+c fusion: the kernels spell out every fmaf they want
@@ -44,7 +46,7 @@ def sources_sha16() -> str:
     import hashlib
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h")))
-    files += PUBLIC_HEADERS + LATER_HEADERS + OUTLIER_HEADERS + GICP_HEADERS + FPFH_HEADERS + MATCH_HEADERS + FGR_HEADERS + GRID_HEADERS + GRIDNN_HEADERS + VOXEL_SORT_HEADERS + RADIUS_HEADERS + ROWS_HEADERS + DBSCAN_HEADERS + SEGMENT_HEADERS + ORIENT_HEADERS + ISS_HEADERS + QUERY_HEADERS
+    files += PUBLIC_HEADERS + LATER_HEADERS + OUTLIER_HEADERS + GICP_HEADERS + FPFH_HEADERS + MATCH_HEADERS + FGR_HEADERS + GRID_HEADERS + GRIDNN_HEADERS + VOXEL_SORT_HEADERS + RADIUS_HEADERS + ROWS_HEADERS + DBSCAN_HEADERS + SEGMENT_HEADERS + ORIENT_HEADERS + ISS_HEADERS + QUERY_HEADERS + SUPPORT_HEADERS
     for f in files:
         h.update(os.path.basename(f).encode())
         with open(f, "rb") as fh:
@@ -104,7 +106,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     jobs, want = [], {}
     for src in sources():
         obj = os.path.join(OBJ, os.path.basename(src)[:-4] + ".o")
-        want[obj] = _digest([src] + hdrs, flags)
+        own = SUPPORT_HEADERS if os.path.basename(src) == "support.hip" else []
+        want[obj] = _digest([src] + hdrs + own, flags)
         if (force or not os.path.exists(obj) or not os.path.exists(obj[:-2] + ".remarks") or _recorded(obj + ".sha") != want[obj]):
             jobs.append((src, obj))
 

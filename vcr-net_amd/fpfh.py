@@ -83,7 +83,7 @@ def fpfh(xyz4, idx, spfh, radius=0.0, guard=0, prefill=None):
 
 
 def compute_fpfh_feature(xyz, normals=None, k=30, radius=None, want_normals=False, want_idx=False, search="knn", max_nn=None,
-                         capacity=None):
+                         capacity=None, queries=None, query_index=None, query_normals=None, support=None):
     """The 33-bin Fast Point Feature Histogram of every point of xyz [B,3,N] (device tensor, up to 131 072 points a cloud) from
     its k nearest neighbours: Open3D's compute_fpfh_feature, in fp64 on the device.  Returns float32 [B,33,N] -- three groups
     of 11 bins, each group of a point summing to 200 where the point and a neighbour have pairs to count; with want_normals
@@ -102,9 +102,38 @@ def compute_fpfh_feature(xyz, normals=None, k=30, radius=None, want_normals=Fals
     length: Open3D's KDTreeSearchParamRadius), or with max_nn=m (any integer >= 1) the nearest min(n_i, m) of them -- Open3D's
     KDTreeSearchParamHybrid(radius, max_nn = m + 1), without the 62 of k.  ONE ``search_radius(xyz, radius, capacity=capacity)``
     serves the normals (where they are not given) and both passes; k is not read; want_idx returns the (idx, row_start, total)
-    triple.  max_nn and capacity belong to this search alone."""
+    triple.  max_nn and capacity belong to this search alone.
+    queries / query_index (search="radius" alone): the features of M CENTRES over xyz as the SUPPORT
+    cloud -> float32 [B,33,M]; PCL's setInputCloud(centres) + setSearchSurface(xyz).  queries [B,3,M] are positions, points of
+    the cloud or not (voxel centroids over the full-resolution cloud, say).  query_index int32 [B,M] says which support point
+    each query is, -1 for none; given without queries it gathers the positions, NaN where it is -1 --
+    ``compute_iss_keypoints``' index can be passed directly, and a NaN centre's feature is NaN.  A query with an index has that
+    point left out of its own neighbourhood, as in the self form: max_nn=m is "the nearest m OTHER points"; a query without one
+    counts a point at its position in its simplified histogram (and skips it, at distance 0, in the weighted sum).
+    query_normals [B,3,M]: the centres' normals; None takes the support's normal at the index where there is one and estimates
+    the others from the query's own row.  With queries = xyz and query_index = arange the result is the self form's, bit for
+    bit; a subset of indices returns the self form's columns.
+    support: how the neighbours' histograms are obtained.  "all": one self search of the whole support and its histograms;
+    only the centres' passes are M-sized.  "needed": the histograms of the points in the centres' rows alone -- the query
+    search, a compaction of the needed points, a second query search from them --; it needs given `normals`.  None picks
+    (``support.plan``).  Both return the same bits.  capacity there: None (one synchronisation a search), an int for both
+    searches or a pair (the queries' rows, the needed points' or the support's rows): no synchronisation; a cloud whose rows
+    did not fit in either search comes back all NaN and nothing raises.  want_normals and want_idx are not served there."""
     api = "compute_fpfh_feature"
     extension.check_cloud(api, "xyz", xyz)
+    if queries is not None or query_index is not None or query_normals is not None or support is not None:
+        from . import support as at
+        if search != "radius":
+            raise VcrHipError(f'{api}: queries, query_index, query_normals and support belong to search="radius", got '
+                              f"search={search!r}")
+        if queries is None and query_index is None:
+            raise VcrHipError(f"{api}: query_normals and support belong to queries= or query_index=; neither is given")
+        if want_normals or want_idx:
+            raise VcrHipError(f"{api}: want_normals and want_idx are not served with queries= or query_index=")
+        if radius is None:
+            raise VcrHipError(f'{api}: search="radius" needs a radius')
+        rows.check_max_nn(api, max_nn)
+        return at.fpfh_at(api, xyz, normals, radius, max_nn, capacity, queries, query_index, query_normals, support)
     if rows.radius_arguments(api, search, radius, max_nn, capacity):
         return _compute_fpfh_radius(api, xyz, normals, radius, max_nn, capacity, want_normals, want_idx)
     grid.check_search(api, search)

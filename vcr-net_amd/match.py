@@ -181,8 +181,8 @@ def ransac_correspondences(src, tgt, corr, max_dist, trials=100000, similarity=0
 
 def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials=100000, similarity=0.9, seed=0, refine=None,
                       refine_method="point_to_point", src_normals=None, tgt_normals=None, method="ransac", fgr=None,
-                      centre=False, search="knn", nn_search="scan", max_nn=None, keypoints=None, iss=None, capacity=None,
-                      orient=None, orient_k=12):
+                      centre=False, search="knn", nn_search="scan", max_nn=None, keypoints=None, iss=None, describe="all",
+                      capacity=None, orient=None, orient_k=12):
     """Register two clouds of any two sizes with neither a network nor a starting pose: src [B,3,Ns], tgt [B,3,Nt] (float32
     device tensors).  compute_fpfh_feature(k, radius) on both, match_features(mutual), ransac_correspondences(max_dist,
     trials, similarity, seed), then score_registration at max_dist on the FULL clouds (Open3D's closing evaluation).
@@ -226,7 +226,16 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     dict of its keywords (salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, capacity, cell) -- picks the source's
     keypoints, and directly behind match_features corr[b, i] becomes -1 where source point i is not one: the RANSAC or FGR
     draws from the keypoints' pairs alone.  The features are still computed on the whole clouds and the target is searched
-    whole; the score and refine steps use every point.  Under orient="tangent" both runs take the same mask."""
+    whole; the score and refine steps use every point.  Under orient="tangent" both runs take the same mask.
+    describe: "all" is that path.  "keypoints" (needs keypoints="iss" and search="radius") computes the
+    SOURCE's features at the keypoints alone -- ``compute_fpfh_feature(src, ..., query_index=index)`` with
+    ``compute_iss_keypoints``' index, the count left on the device: the padded slots are NaN centres with empty rows and NaN
+    features, which never win a match.  Given normals, and under orient="tangent" the oriented ones, are the whole cloud's.
+    match_features runs on those [B,33,Ns] columns against the whole target and its result is scattered to corr [B,Ns], -1
+    elsewhere.  With mutual=False every key equals describe="all" bit for bit.  With mutual=True the reverse search runs among
+    the KEYPOINTS' features alone: a pair (i, j) is kept where keypoint i is the nearest KEYPOINT of j, not the nearest source
+    point -- a different definition, and the one a keypoint pipeline means; "all" asks more of a pair and keeps fewer.  The
+    target side stays whole."""
     from . import grid, gridnn, rows
     feat = dict(k=k, radius=radius, search=search)          # what both compute_fpfh_feature calls take
     if rows.radius_arguments("register_features", search, radius, max_nn, capacity):
@@ -239,13 +248,18 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     if isinstance(orient_k, bool) or not isinstance(orient_k, int) or orient_k < 1:
         raise VcrHipError(f"register_features: orient_k must be an integer >= 1, got {orient_k!r}")
     iss = _keypoint_arguments("register_features", keypoints, iss)
+    if describe not in ("all", "keypoints") or not isinstance(describe, str):
+        raise VcrHipError(f'register_features: describe must be "all" or "keypoints", got {describe!r}')
+    if describe == "keypoints" and (keypoints != "iss" or search != "radius"):
+        raise VcrHipError(f'register_features: describe="keypoints" needs keypoints="iss" and search="radius", got '
+                          f"keypoints={keypoints!r}, search={search!r}")
     if centre is not False and centre is not None:
         return _register_centred(src, tgt, max_dist, centre, refine,
                                  dict(k=k, radius=radius, mutual=mutual, trials=trials, similarity=similarity, seed=seed,
                                       refine=refine, refine_method=refine_method, src_normals=src_normals,
                                       tgt_normals=tgt_normals, method=method, fgr=fgr, search=search, nn_search=nn_search,
                                       max_nn=max_nn, capacity=capacity, orient=orient, orient_k=orient_k,
-                                      keypoints=keypoints, iss=iss or None))
+                                      keypoints=keypoints, iss=iss or None, describe=describe))
     from .fpfh import compute_fpfh_feature
     from .refine import refine_registration
     from .score import score_registration
@@ -256,19 +270,19 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
         raise VcrHipError(f'{api}: method must be "ransac" or "fgr", got {method!r}')
     if method == "fgr":
         return _register_fgr(api, src, tgt, max_dist, feat, mutual, refine, refine_method, src_normals, tgt_normals, fgr, nn_search,
-                             orient, orient_k, keypoints, iss)
+                             orient, orient_k, keypoints, iss, describe)
     if fgr is not None:
         raise VcrHipError(f'{api}: fgr= holds the keywords of method="fgr"; the method is "ransac"')
     _ransac_checks(api, src, tgt, None, max_dist, trials, similarity, seed, given_corr=False)
-    keep = _keypoint_mask(src, keypoints, iss)
+    keep, index = _keypoint_mask(src, keypoints, iss, describe)
 
     def tail(src_feat, tgt_feat):
-        corr = _masked(match_features(src_feat, tgt_feat, mutual=mutual), keep)
+        corr = _placed(match_features(src_feat, tgt_feat, mutual=mutual), keep, index)
         r = ransac_correspondences(src, tgt, corr, max_dist, trials, similarity, seed)
         res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist, search=nn_search))
         res.update(R=r["R"], t=r["t"], best_trial=r["best_trial"], pairs=r["pairs"], ransac_inliers=r["inliers"], corr=corr)
         return res
-    res = _both_signs(src, tgt, src_normals, tgt_normals, feat, orient, orient_k, tail)
+    res = _both_signs(src, tgt, src_normals, tgt_normals, feat, orient, orient_k, tail, index)
     if refine is not None:
         res["refined"] = refine_registration(src, tgt, res["R"], res["t"], float(refine), method=refine_method, search=nn_search)
     return res
@@ -293,13 +307,15 @@ def _keypoint_arguments(api, keypoints, iss):
     return iss
 
 
-def _keypoint_mask(src, keypoints, iss):
-    """bool [B,Ns]: the source points that keep their match; None where every point does."""
+def _keypoint_mask(src, keypoints, iss, describe="all"):
+    """-> (bool [B,Ns]: the source points that keep their match, None where every point does; with describe="keypoints" the
+    keypoints' index int32 [B,Ns], -1 behind the count, else None)."""
     if keypoints is None:
-        return None
+        return None, None
     from .iss import compute_iss_keypoints
     try:
-        return compute_iss_keypoints(src, want_flag=True, **iss)[3] > 0
+        got = compute_iss_keypoints(src, want_flag=True, **iss)
+        return got[3] > 0, (got[2] if describe == "keypoints" else None)
     except VcrHipError as e:
         raise VcrHipError(str(e).replace("compute_iss_keypoints", 'register_features (keypoints="iss")', 1)) from None
 
@@ -307,6 +323,19 @@ def _keypoint_mask(src, keypoints, iss):
 def _masked(corr, keep):
     """match_features' corr with -1 (no partner) where keep is False: a device `where`."""
     return corr if keep is None else torch.where(keep, corr, torch.full_like(corr, -1))
+
+
+def _placed(corr, keep, index):
+    """corr [B,Ns] in the source's numbering: match_features' result masked (index None: it already is in that numbering), or
+    -- the matches of the keypoints' columns -- scattered to the keypoints' indices, -1 elsewhere and for slots behind the count."""
+    if index is None:
+        return _masked(corr, keep)
+    B, Ns = index.shape
+    ok = index >= 0
+    at = torch.where(ok, index, torch.full_like(index, Ns)).long()       # (a padded slot goes behind the end)
+    out = torch.full((B, Ns + 1), -1, dtype=corr.dtype, device=corr.device)
+    out.scatter_(1, at, torch.where(ok, corr, torch.full_like(corr, -1)))
+    return out[:, :Ns].contiguous()
 
 
 def _estimated_normals(xyz, feat):
@@ -317,26 +346,27 @@ def _estimated_normals(xyz, feat):
     return estimate_normals(xyz, feat["k"], search=feat["search"])
 
 
-def _both_signs(src, tgt, src_normals, tgt_normals, feat, orient, orient_k, tail):
+def _both_signs(src, tgt, src_normals, tgt_normals, feat, orient, orient_k, tail, src_index=None):
     """The features of both clouds (feat: the keywords of both compute_fpfh_feature calls) and tail(src_feat, tgt_feat) -> the
     result's dict: matching, RANSAC or FGR, score.  orient="tangent": a side without given normals has them estimated and
     oriented first; where there is such a side the tail runs a second time on the features of the source's normals negated, and
     every entry is taken per cloud from the run with the higher fitness -- the lower inlier_rmse where the fitness is equal --,
-    the first among equals; `flipped` bool [B]."""
+    the first among equals; `flipped` bool [B].  src_index: describe="keypoints" -- the source's features at those indices alone."""
     from .fpfh import compute_fpfh_feature
+    at = {} if src_index is None else dict(query_index=src_index)
     if orient is None:
-        return tail(compute_fpfh_feature(src, src_normals, **feat), compute_fpfh_feature(tgt, tgt_normals, **feat))
+        return tail(compute_fpfh_feature(src, src_normals, **feat, **at), compute_fpfh_feature(tgt, tgt_normals, **feat))
     from .orient import orient_normals_consistent_tangent_plane
     twice = src_normals is None or tgt_normals is None
     if src_normals is None:
         src_normals = orient_normals_consistent_tangent_plane(src, _estimated_normals(src, feat), k=orient_k)
     if tgt_normals is None:
         tgt_normals = orient_normals_consistent_tangent_plane(tgt, _estimated_normals(tgt, feat), k=orient_k)
-    src_feat, tgt_feat = compute_fpfh_feature(src, src_normals, **feat), compute_fpfh_feature(tgt, tgt_normals, **feat)
+    src_feat, tgt_feat = compute_fpfh_feature(src, src_normals, **feat, **at), compute_fpfh_feature(tgt, tgt_normals, **feat)
     res = tail(src_feat, tgt_feat)
     flipped = torch.zeros(src.shape[0], dtype=torch.bool, device=res["fitness"].device)
     if twice:
-        other = tail(compute_fpfh_feature(src, -src_normals, **feat), tgt_feat)
+        other = tail(compute_fpfh_feature(src, -src_normals, **feat, **at), tgt_feat)
         # fitness first, then the lower inlier_rmse (Open3D's order of two RANSAC results): on clean copies BOTH runs can end
         # with every point an inlier -- a few correct matches among many wrong ones still find a pose -- and the fitness ties
         flipped = (other["fitness"] > res["fitness"]) | ((other["fitness"] == res["fitness"])
@@ -348,7 +378,7 @@ def _both_signs(src, tgt, src_normals, tgt_normals, feat, orient, orient_k, tail
 
 
 def _register_fgr(api, src, tgt, max_dist, feat, mutual, refine, refine_method, src_normals, tgt_normals, kw, nn_search="scan",
-                  orient=None, orient_k=12, keypoints=None, iss=None):
+                  orient=None, orient_k=12, keypoints=None, iss=None, describe="all"):
     """register_features with method="fgr": the same chain with fast_global_registration in the RANSAC's place.  feat: the
     keywords of both compute_fpfh_feature calls."""
     from . import fgr as F
@@ -365,15 +395,15 @@ def _register_fgr(api, src, tgt, max_dist, feat, mutual, refine, refine_method, 
         raise VcrHipError(f"{api}: max_dist must be finite and >= 0, got {max_dist}")
     F._fgr_checks(api, src, tgt, None, kw["tuple_scale"], kw["max_tuples"], kw["iterations"], kw["division_factor"], kw["mu_floor"],
                   kw["tuple_trials"], kw["seed"], given_corr=False)
-    keep = _keypoint_mask(src, keypoints, iss)
+    keep, index = _keypoint_mask(src, keypoints, iss, describe)
 
     def tail(src_feat, tgt_feat):
-        corr = _masked(match_features(src_feat, tgt_feat, mutual=mutual), keep)
+        corr = _placed(match_features(src_feat, tgt_feat, mutual=mutual), keep, index)
         r = F.fast_global_registration(src, tgt, corr, **kw)
         res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist, search=nn_search))
         res.update(R=r["R"], t=r["t"], pairs=r["pairs"], tuples=r["tuples"], used=r["used"], status=r["status"], corr=corr)
         return res
-    res = _both_signs(src, tgt, src_normals, tgt_normals, feat, orient, orient_k, tail)
+    res = _both_signs(src, tgt, src_normals, tgt_normals, feat, orient, orient_k, tail, index)
     if refine is not None:
         res["refined"] = refine_registration(src, tgt, res["R"], res["t"], float(refine), method=refine_method, search=nn_search)
     return res

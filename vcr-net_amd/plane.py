@@ -68,7 +68,7 @@ def normals(xyz4, idx, viewpoint=None, want_curvature=True, guard=0, prefill=Non
 
 
 def estimate_normals(xyz, k=20, viewpoint=None, want_curvature=False, want_idx=False, search="knn", radius=None, max_nn=None,
-                     capacity=None):
+                     capacity=None, queries=None):
     """A unit normal per point of xyz [B,3,N] (device tensor) from its k nearest neighbours: the eigenvector of the smallest
     eigenvalue of the covariance of the point and those neighbours (Open3D's estimate_normals with a kNN search), in fp64 on
     the device.  Returns normals float32 [B,3,N]; with want_curvature also the surface variation lambda0 / (lambda0 + lambda1 +
@@ -88,10 +88,17 @@ def estimate_normals(xyz, k=20, viewpoint=None, want_curvature=False, want_idx=F
     does.  k is not read.  A point with fewer than two neighbours gets (0, 0, 1), curvature 0.  capacity: ``search_radius``'s
     (None reads the rows' total back once; an integer is one call without a synchronisation, and a cloud whose rows exceed it
     comes back NaN).  want_idx then returns the (idx, row_start, total) triple in idx's place.  radius, max_nn and capacity
-    belong to this search alone."""
+    belong to this search alone.
+    queries=[B,3,M] (search="radius" alone): the normals of the surface xyz AT those positions -> [B,3,M]
+    (with want_curvature also [B,M]), each from the points within `radius` of the query (``search_radius(queries=)``), the
+    viewpoint rule taken at the query's position.  A query is a position, not an index: a point at the query's position is a
+    point of its neighbourhood, max_nn=m keeps the nearest m points, and fewer than three points give (0, 0, 1), curvature 0.
+    A query with a NaN or infinite coordinate gets NaN.  want_idx is not served there."""
     if not torch.is_tensor(xyz) or xyz.dim() != 3 or xyz.shape[1] != 3:
         raise VcrHipError(f"estimate_normals: xyz must be a [B, 3, N] point cloud, got "
                           f"{tuple(xyz.shape) if torch.is_tensor(xyz) else type(xyz).__name__}")
+    if queries is not None:
+        return _estimate_normals_queries(xyz, search, radius, max_nn, capacity, viewpoint, want_curvature, want_idx, queries)
     if rows.radius_arguments("estimate_normals", search, radius, max_nn, capacity):
         return _estimate_normals_radius(xyz, radius, max_nn, capacity, viewpoint, want_curvature, want_idx)
     if radius is not None:
@@ -114,6 +121,26 @@ def estimate_normals(xyz, k=20, viewpoint=None, want_curvature=False, want_idx=F
     nrm, cur = normals(xyz4, idx, viewpoint, want_curvature=want_curvature)
     res = (nrm,) + ((cur,) if want_curvature else ()) + ((idx,) if want_idx else ())
     return res[0] if len(res) == 1 else res
+
+
+def _estimate_normals_queries(xyz, search, radius, max_nn, capacity, viewpoint, want_curvature, want_idx, queries):
+    """estimate_normals(queries=): one search_radius from the queries, then vcr_support_normals_f32 on its rows."""
+    from . import support
+    api = "estimate_normals"
+    if search != "radius":
+        raise VcrHipError(f'{api}: queries belongs to search="radius", got search={search!r}')
+    rows.radius_arguments(api, search, radius, max_nn, capacity)
+    if want_idx:
+        raise VcrHipError(f"{api}: want_idx is not served with queries=")
+    B, _, _ = support.query_arguments(api, xyz, queries, None)
+    if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 0):
+        raise VcrHipError(f"{api}: capacity must be None or an integer >= 0, got {capacity!r}")
+    if not (xyz.is_cuda and queries.is_cuda):
+        raise VcrHipError(f"{api} runs on the MI355X HIP path only; move the cloud and the queries to cuda "
+                          "(there is no CPU fallback by design)")
+    if viewpoint is not None and (not torch.is_tensor(viewpoint) or tuple(viewpoint.shape) != (B, 3) or not viewpoint.is_cuda):
+        raise VcrHipError(f"{api}: viewpoint must be a device tensor [B, 3] with B = {B}")
+    return support.query_normals_of(xyz, queries, radius, max_nn, capacity, viewpoint, want_curvature)
 
 
 def _estimate_normals_radius(xyz, radius, max_nn, capacity, viewpoint, want_curvature, want_idx):
