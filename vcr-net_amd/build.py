@@ -31,6 +31,9 @@ ISS_HEADERS = [os.path.join(INCLUDE, "keypoint", f) for f in ("vcr_hip_iss.h",)]
 QUERY_HEADERS = [os.path.join(INCLUDE, "query", f) for f in ("vcr_hip_query.h",)]   # (... and include/keypoint/'s)
 # (... and include/query/'s; tests hold query.o's digest to the lists above, so this one enters the digest of support.o ALONE)
 SUPPORT_HEADERS = [os.path.join(INCLUDE, "support", f) for f in ("vcr_hip_support.h",)]
+# (support.o's digest and the profiles' digest are pinned as well: this one enters the digests of its own two objects ALONE)
+COLORED_HEADERS = [os.path.join(INCLUDE, "colored", f) for f in ("vcr_hip_colored.h",)]
+OWN_HEADERS = {"support.hip": SUPPORT_HEADERS, "color_gradient.hip": COLORED_HEADERS, "refine_colored.hip": COLORED_HEADERS}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off"]   # no silent a*b+c fusion: the kernels spell out every fmaf they want
@@ -106,7 +109,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     jobs, want = [], {}
     for src in sources():
         obj = os.path.join(OBJ, os.path.basename(src)[:-4] + ".o")
-        own = SUPPORT_HEADERS if os.path.basename(src) == "support.hip" else []
+        own = OWN_HEADERS.get(os.path.basename(src), [])
         want[obj] = _digest([src] + hdrs + own, flags)
         if (force or not os.path.exists(obj) or not os.path.exists(obj[:-2] + ".remarks") or _recorded(obj + ".sha") != want[obj]):
             jobs.append((src, obj))

@@ -1,6 +1,6 @@
 // The round of the refinements on the full clouds, written once: refine.hip (vcr_refine_f32, point to point),
-// refine_plane.hip (vcr_refine_plane_f32, point to plane) and refine_gicp.hip (vcr_refine_gicp_f32, plane to plane) run the
-// same loop and differ in the FIT -- the sums a round accumulates over its inliers and the solve behind them.  Here: the per-cloud state in the workspace and the kernel that
+// refine_plane.hip (vcr_refine_plane_f32, point to plane), refine_gicp.hip (vcr_refine_gicp_f32, plane to plane) and
+// refine_colored.hip (vcr_refine_colored_f32, colour and shape) run the same loop and differ in the FIT -- the sums a round accumulates over its inliers and the solve behind them.  Here: the per-cloud state in the workspace and the kernel that
 // initialises it, the plan (argument checks, form of the search, workspace layout), the body of the merge kernel, the parts of
 // the per-cloud kernel that do not solve (the sum of the partials, the evaluation and the stop test, the composed pose), and
 // the host driver behind the three entry points of each header.
@@ -11,8 +11,9 @@
 //   gather()                     what it reads at the neighbour's index besides the neighbour, a coordinate at a time
 //   source()                     what it reads at the SOURCE point's own index n besides the point, likewise
 //   sums()                       values 2 ... VALUES - 1 of one source point -- from an RfPoint: the moved point, the neighbour,
-//                                what gather() and source() read, the fp32 pose the merge holds and whether the lane is an
-//                                inlier -- handed to `put` one at a time.  A lane that is no inlier must contribute exact zeros:
+//                                what gather() and source() read, the fp32 pose the merge holds, whether the lane is an
+//                                inlier, and the indices (cloud, source point, neighbour) by which a fit that reads more
+//                                than two triples fetches the rest -- handed to `put` one at a time.  A lane that is no inlier must contribute exact zeros:
 //                                its four triples are zero, which is enough for a fit whose every term is a product of them.
 //   Args, take()                 (host) the public argument struct, and the copy of it the call works on
 // The kernels themselves stay in the fits' .hip files under their own names, as wrappers of the bodies below.
@@ -65,7 +66,8 @@ struct RfPoint {                                           // one lane of the me
   const float* pc; const float* qc; const float* gc; const float* sc;   // [3] each: moved point, neighbour, gather()'s, source()'s
   const float* R;                                          // [9], the cloud's fp32 pose the scan ran under (read by inliers only)
   bool in;
-};
+  int b, n, bi;                                            // the cloud, the source point, its neighbour (bi in [0, Nt) where `in`): a fit
+};                                                         // that reads more than gather() and source() carry fetches it by these
 
 template <class Fit>
 struct RfMerge {
@@ -121,7 +123,7 @@ __device__ __forceinline__ void rf_merge_body(const RfMerge<Fit>& p) {
   };
   put(0, in ? (double)best : 0.);
   put(1, in ? 1. : 0.);
-  p.fit.sums(RfPoint{pc, qc, gc, sc, r, in}, put);
+  p.fit.sums(RfPoint{pc, qc, gc, sc, r, in, b, n, bi}, put);
   __syncthreads();
   if (t < Fit::VALUES) {
     double s = red[0][t];
