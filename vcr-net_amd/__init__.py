@@ -16,7 +16,8 @@ __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "sco
            "match_features", "ransac_correspondences", "register_features", "fast_global_registration", "centred",
            "uncentred_pose", "search_knn", "search_radius", "cluster_dbscan", "largest_cluster", "segment_plane",
            "split_by_plane", "segment_planes", "orient_normals_consistent_tangent_plane", "compute_iss_keypoints",
-           "model_resolution", "compute_point_cloud_distance", "compute_color_gradient", "refine_registration_colored"]
+           "model_resolution", "compute_point_cloud_distance", "compute_color_gradient", "refine_registration_colored",
+           "refine_registration_robust", "information_matrix"]
 
 
 def __getattr__(name):
@@ -75,6 +76,9 @@ def __getattr__(name):
     if name in ("compute_color_gradient", "refine_registration_colored"):
         from . import colored
         return getattr(colored, name)
+    if name in ("refine_registration_robust", "information_matrix"):
+        from . import robust
+        return getattr(robust, name)
     if name in ("centred", "uncentred_pose"):
         from . import centre
         return getattr(centre, name)

@@ -33,7 +33,10 @@ QUERY_HEADERS = [os.path.join(INCLUDE, "query", f) for f in ("vcr_hip_query.h",)
 SUPPORT_HEADERS = [os.path.join(INCLUDE, "support", f) for f in ("vcr_hip_support.h",)]
 # (support.o's digest and the profiles' digest are pinned as well: this one enters the digests of its own two objects ALONE)
 COLORED_HEADERS = [os.path.join(INCLUDE, "colored", f) for f in ("vcr_hip_colored.h",)]
-OWN_HEADERS = {"support.hip": SUPPORT_HEADERS, "color_gradient.hip": COLORED_HEADERS, "refine_colored.hip": COLORED_HEADERS}
+# (... and so are the colored objects': this one enters the digest of refine_robust.o ALONE)
+ROBUST_HEADERS = [os.path.join(INCLUDE, "robust", f) for f in ("vcr_hip_robust.h",)]
+OWN_HEADERS = {"support.hip": SUPPORT_HEADERS, "color_gradient.hip": COLORED_HEADERS, "refine_colored.hip": COLORED_HEADERS,
+               "refine_robust.hip": ROBUST_HEADERS}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off"]   # no silent a*b+c fusion: the kernels spell out every fmaf they want
