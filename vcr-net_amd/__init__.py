@@ -17,7 +17,8 @@ __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "sco
            "uncentred_pose", "search_knn", "search_radius", "cluster_dbscan", "largest_cluster", "segment_plane",
            "split_by_plane", "segment_planes", "orient_normals_consistent_tangent_plane", "compute_iss_keypoints",
            "model_resolution", "compute_point_cloud_distance", "compute_color_gradient", "refine_registration_colored",
-           "refine_registration_robust", "information_matrix"]
+           "refine_registration_robust", "information_matrix", "optimize_pose_graph", "pose_graph_from_clouds",
+           "register_multiway"]
 
 
 def __getattr__(name):
@@ -79,6 +80,9 @@ def __getattr__(name):
     if name in ("refine_registration_robust", "information_matrix"):
         from . import robust
         return getattr(robust, name)
+    if name in ("optimize_pose_graph", "pose_graph_from_clouds", "register_multiway"):
+        from . import posegraph
+        return getattr(posegraph, name)
     if name in ("centred", "uncentred_pose"):
         from . import centre
         return getattr(centre, name)
