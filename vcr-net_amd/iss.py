@@ -81,9 +81,16 @@ def check_gamma(api, name, gamma):
     return g
 
 
-def check_arguments(api, salient_radius=None, non_max_radius=None, gamma_21=0.975, gamma_32=0.975, min_neighbors=5, **_):
+def check_arguments(api, salient_radius=None, non_max_radius=None, gamma_21=0.975, gamma_32=0.975, min_neighbors=5,
+                    border_radius=None, normal_radius=None, border_angle=90.0, **_):
     """What compute_iss_keypoints asks of its numbers, under the caller's name -> (gamma_21, gamma_32) as floats."""
-    for name, r in (("salient_radius", salient_radius), ("non_max_radius", non_max_radius)):
+    if border_radius is None and normal_radius is not None:
+        raise VcrHipError(f"{api}: normal_radius belongs to border_radius, which is None")
+    if border_radius is not None:
+        from .border import check_threshold
+        check_threshold(api, "border_angle", border_angle)
+    for name, r in (("salient_radius", salient_radius), ("non_max_radius", non_max_radius), ("border_radius", border_radius),
+                    ("normal_radius", normal_radius)):
         if r is not None:
             try:
                 radius._radius(api, r)
@@ -246,8 +253,38 @@ def _search(api, xyz, r, want_d2, capacity, cell):
         raise VcrHipError(str(e).replace("search_radius", api, 1)) from None
 
 
+def _border_near(api, xyz, xyz4, searched, border_radius, normal_radius, border_angle, normals, capacity, cell):
+    """PCL's border rule -> near int32 [B,N]: 1 where a boundary point lies within border_radius of the point, itself included.
+    The boundary is ``border``'s at border_radius over ALL the points within it and its default of 3 points a neighbourhood.
+    searched: None, or (radius, idx, row_start, total, d2) of a search already made: with normals given and border_radius within
+    that radius, the three passes read the d2 prefix of those rows and nothing is searched."""
+    from . import border, rows
+    br, br2 = radius._radius(api, border_radius)
+    thr = border.radians(border_angle)
+    if normals is not None and searched is not None and br <= searched[0]:
+        _, idx, row_start, total, d2 = searched
+        flag, _ = border.boundary_rows(xyz4, normals, idx, row_start, total, 3, thr, d2=d2, r2=br2)
+        return border.near_rows(flag, idx, row_start, total, d2=d2, r2=br2)["near"]
+    idx, row_start, total = _search(api, xyz, br, False, capacity, cell)
+    if normals is None:
+        nr = br if normal_radius is None else float(normal_radius)
+        over = (idx, row_start, total) if nr == br else _search(api, xyz, nr, False, capacity, cell)
+        normals = rows.normals(xyz4, *over, want_curvature=False)[0]
+    flag, _ = border.boundary_rows(xyz4, normals, idx, row_start, total, 3, thr)
+    return border.near_rows(flag, idx, row_start, total)["near"]
+
+
+def _without_border(sal, near):
+    """The saliency with 0 where the point is near the boundary, NaN over a cloud whose boundary was not served (the suppression
+    voids it)."""
+    zero, nan = torch.zeros((), dtype=sal.dtype, device=sal.device), torch.full((), float("nan"), dtype=sal.dtype, device=sal.device)
+    sal = torch.where(near > 0, zero, sal)
+    return torch.where(near < 0, nan, sal)
+
+
 def compute_iss_keypoints(xyz, salient_radius=None, non_max_radius=None, gamma_21=0.975, gamma_32=0.975, min_neighbors=5,
-                          capacity=None, cell=None, want_flag=False, want_saliency=False):
+                          capacity=None, cell=None, want_flag=False, want_saliency=False, border_radius=None, normal_radius=None,
+                          border_angle=90.0, normals=None):
     """ISS keypoints of every cloud of xyz [B,3,N] (device tensor, up to 131 072 points a cloud): Open3D's
     compute_iss_keypoints(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors).  Returns (points, count, index) as
     ``remove_radius_outlier`` returns them -- the keypoints compacted in ascending index order, NaN / -1 behind count[b];
@@ -267,11 +304,24 @@ def compute_iss_keypoints(xyz, salient_radius=None, non_max_radius=None, gamma_2
     every flag -2 and every saliency NaN.  cell: the search grid's edge, as ``search_radius``' (it never changes the result).
     A radius of None is Open3D's default, 6 (salient) and 4 (non-max) times ``model_resolution``, rounded to fp32 per cloud:
     that reads the resolutions back -- one more host synchronisation -- and, because ``search_radius`` takes one radius a call,
-    runs a batch of B > 1 cloud by cloud.  It needs N >= 2."""
+    runs a batch of B > 1 cloud by cloud.  It needs N >= 2.
+    border_radius (None changes nothing: the same launches, the same bits) is PCL's rule against the rim of
+    a partial scan, whose half-empty neighbourhoods look salient: a point with a boundary point (``compute_boundary_points`` at
+    border_radius over all the points within it, border_angle in degrees) within border_radius of it, itself included, is not
+    salient -- its saliency is 0 before the suppression, and in what want_saliency returns.  normals [B,3,N] serve the boundary;
+    None estimates them over normal_radius (default border_radius).  With normals given and border_radius <= the larger radius
+    searched already, the boundary reads a prefix of those rows; otherwise it costs one search more (two where normal_radius
+    differs)."""
     api = "compute_iss_keypoints"
     radius._cloud(api, xyz)
-    g21, g32 = check_arguments(api, salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors)
+    g21, g32 = check_arguments(api, salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, border_radius, normal_radius,
+                               border_angle)
     B, _, N = xyz.shape
+    if border_radius is not None:
+        from .border import check_normals
+        check_normals(api, normals, B, N)
+    elif normals is not None:
+        raise VcrHipError(f"{api}: normals belong to border_radius, which is None")
     if (salient_radius is None or non_max_radius is None) and N < 2:
         raise VcrHipError(f"{api}: the default radii come from model_resolution, which needs at least 2 points, got N = {N}")
     radius._on_device(api, xyz)
@@ -282,17 +332,28 @@ def compute_iss_keypoints(xyz, salient_radius=None, non_max_radius=None, gamma_2
         for b in range(B):
             sr = float(torch.tensor(6.0 * float(res[b]), dtype=torch.float32)) if salient_radius is None else salient_radius
             nr = float(torch.tensor(4.0 * float(res[b]), dtype=torch.float32)) if non_max_radius is None else non_max_radius
-            per.append(compute_iss_keypoints(xyz[b:b + 1], sr, nr, g21, g32, min_neighbors, capacity, cell, True, True))
+            per.append(compute_iss_keypoints(xyz[b:b + 1], sr, nr, g21, g32, min_neighbors, capacity, cell, True, True,
+                                             border_radius, normal_radius, border_angle,
+                                             None if normals is None else normals[b:b + 1]))
         got = tuple(torch.cat([p[j] for p in per]) for j in range(5))
     else:
         sr, nr = float(salient_radius), float(non_max_radius)
         xyz4 = native.to_rows4(xyz)
+        if border_radius is not None and normals is not None:
+            native.same_device(xyz, normals)
+            normals = normals.contiguous().float()
         if nr <= sr:
             idx, row_start, total, d2 = _search(api, xyz, sr, True, capacity, cell)
             sal = saliency_rows(xyz4, idx, row_start, total, g21, g32, min_neighbors)["saliency"]
+            if border_radius is not None:
+                sal = _without_border(sal, _border_near(api, xyz, xyz4, (sr, idx, row_start, total, d2), border_radius,
+                                                        normal_radius, border_angle, normals, capacity, cell))
             flag = nms_rows(idx, row_start, total, sal, min_neighbors, d2=d2, r2_nm=radius._radius(api, nr)[1])["keypoint"]
         else:
             sal = saliency_rows(xyz4, *_search(api, xyz, sr, False, capacity, cell), g21, g32, min_neighbors)["saliency"]
+            if border_radius is not None:
+                sal = _without_border(sal, _border_near(api, xyz, xyz4, None, border_radius, normal_radius, border_angle, normals,
+                                                        capacity, cell))
             flag = nms_rows(*_search(api, xyz, nr, False, capacity, cell), sal, min_neighbors)["keypoint"]
         o = select(xyz, flag)
         got = (o["points"], o["count"], o["index"], flag, sal)

@@ -223,7 +223,8 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     ``nn_search``: the ``search`` of the score and refine steps: "scan" (the default) or "grid", the target's uniform grid
      -- the same poses and scores bit for bit, faster on large clouds.
     keypoints: None matches every source point.  "iss" (DESIGN.md section 4.27): ``compute_iss_keypoints(src, **iss)`` -- `iss` a
-    dict of its keywords (salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, capacity, cell) -- picks the source's
+    dict of its keywords (salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, capacity, cell, and border_radius,
+    normal_radius, border_angle, normals of its rule against the scan's rim) -- picks the source's
     keypoints, and directly behind match_features corr[b, i] becomes -1 where source point i is not one: the RANSAC or FGR
     draws from the keypoints' pairs alone.  The features are still computed on the whole clouds and the target is searched
     whole; the score and refine steps use every point.  Under orient="tangent" both runs take the same mask.
@@ -288,7 +289,8 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     return res
 
 
-ISS_KEYWORDS = ("salient_radius", "non_max_radius", "gamma_21", "gamma_32", "min_neighbors", "capacity", "cell")
+ISS_KEYWORDS = ("salient_radius", "non_max_radius", "gamma_21", "gamma_32", "min_neighbors", "capacity", "cell", "border_radius",
+                "normal_radius", "border_angle", "normals")
 
 
 def _keypoint_arguments(api, keypoints, iss):
