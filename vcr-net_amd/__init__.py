@@ -18,7 +18,8 @@ __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "sco
            "split_by_plane", "segment_planes", "orient_normals_consistent_tangent_plane", "compute_iss_keypoints",
            "model_resolution", "compute_point_cloud_distance", "compute_color_gradient", "refine_registration_colored",
            "refine_registration_robust", "information_matrix", "optimize_pose_graph", "pose_graph_from_clouds",
-           "register_multiway", "compute_boundary_points", "smooth_mls"]
+           "register_multiway", "compute_boundary_points", "smooth_mls", "consistency_registration",
+           "correspondence_consistency", "prune_correspondences"]
 
 
 def __getattr__(name):
@@ -89,6 +90,9 @@ def __getattr__(name):
     if name == "smooth_mls":
         from .mls import smooth_mls
         return smooth_mls
+    if name in ("consistency_registration", "correspondence_consistency", "prune_correspondences"):
+        from . import consistency
+        return getattr(consistency, name)
     if name in ("centred", "uncentred_pose"):
         from . import centre
         return getattr(centre, name)

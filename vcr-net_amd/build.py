@@ -41,9 +41,11 @@ POSEGRAPH_HEADERS = [os.path.join(INCLUDE, "posegraph", f) for f in ("vcr_hip_po
 BORDER_HEADERS = [os.path.join(INCLUDE, "border", f) for f in ("vcr_hip_border.h",)]
 # (... and border.o's: this one enters the digest of mls.o ALONE)
 MLS_HEADERS = [os.path.join(INCLUDE, "smooth", f) for f in ("vcr_hip_mls.h",)]
+# (... and mls.o's: this one enters the digest of consistency.o ALONE)
+CONSISTENCY_HEADERS = [os.path.join(INCLUDE, "consistency", f) for f in ("vcr_hip_consistency.h",)]
 OWN_HEADERS = {"support.hip": SUPPORT_HEADERS, "color_gradient.hip": COLORED_HEADERS, "refine_colored.hip": COLORED_HEADERS,
                "refine_robust.hip": ROBUST_HEADERS, "posegraph.hip": POSEGRAPH_HEADERS, "border.hip": BORDER_HEADERS,
-               "mls.hip": MLS_HEADERS}
+               "mls.hip": MLS_HEADERS, "consistency.hip": CONSISTENCY_HEADERS}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off"]   # no silent a*b+c fusion: the kernels spell out every fmaf they want

@@ -1,6 +1,7 @@
-// What the two global registrations share in front of their own work (ransac.hip, fgr.hip; include/vcr_hip_match.h and
-// include/vcr_hip_fgr.h state it once each): the pair list of a correspondence array, the hash of the draws and the squared
-// edge length.  One text, so the draws of a seed and the order of the pairs are the same in both.
+// What the global registrations share around their own work (ransac.hip, fgr.hip, consistency.hip; include/vcr_hip_match.h,
+// include/vcr_hip_fgr.h and include/consistency/vcr_hip_consistency.h state it once each): the pair list of a correspondence
+// array, the hash of the draws, the squared edge length and the distance of a pair under an fp32 pose.  One text, so the draws
+// of a seed, the order of the pairs and a pose's count are the same in all of them.
 #pragma once
 #include "wg_scan.h"
 
@@ -61,6 +62,15 @@ __device__ __forceinline__ unsigned rs_pick(unsigned seed, int trial, int j, int
 
 __device__ __forceinline__ float rs_len2(const f32x4& u, const f32x4& v) {
   const float dx = u[0] - v[0], dy = u[1] - v[1], dz = u[2] - v[2];
+  return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+}
+
+// (ransac.hip's and consistency.hip's distance check and count) vcr_hip_score.h's `moved source` and `distance` under the fp32 pose (R row-major, then t)
+__device__ __forceinline__ float rs_d2(const float (&P)[12], float x, float y, float z, float qx, float qy, float qz) {
+  const float px = fmaf(P[2], z, fmaf(P[1], y, P[0] * x)) + P[9];
+  const float py = fmaf(P[5], z, fmaf(P[4], y, P[3] * x)) + P[10];
+  const float pz = fmaf(P[8], z, fmaf(P[7], y, P[6] * x)) + P[11];
+  const float dx = px - qx, dy = py - qy, dz = pz - qz;
   return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
 }
 

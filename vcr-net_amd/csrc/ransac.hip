@@ -33,15 +33,6 @@ struct RsWork {                                            // the workspace, per
 
 __global__ __launch_bounds__(RS_BLOCK) void ransac_pairs_kernel(RsPairs p) { rs_pairs_body(p); }
 
-// vcr_hip_score.h's `moved source` and `distance` under the fp32 pose (R row-major, then t)
-__device__ __forceinline__ float rs_d2(const float (&P)[12], float x, float y, float z, float qx, float qy, float qz) {
-  const float px = fmaf(P[2], z, fmaf(P[1], y, P[0] * x)) + P[9];
-  const float py = fmaf(P[5], z, fmaf(P[4], y, P[3] * x)) + P[10];
-  const float pz = fmaf(P[8], z, fmaf(P[7], y, P[6] * x)) + P[11];
-  const float dx = px - qx, dy = py - qy, dz = pz - qz;
-  return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-}
-
 struct RsTrial {
   RsWork w; int Ns, T; unsigned seed; float max_d2, s2; int edges;
   int* picks;                                              // optional [B][T][3]

@@ -182,7 +182,7 @@ def ransac_correspondences(src, tgt, corr, max_dist, trials=100000, similarity=0
 def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials=100000, similarity=0.9, seed=0, refine=None,
                       refine_method="point_to_point", src_normals=None, tgt_normals=None, method="ransac", fgr=None,
                       centre=False, search="knn", nn_search="scan", max_nn=None, keypoints=None, iss=None, describe="all",
-                      capacity=None, orient=None, orient_k=12):
+                      consistency=None, capacity=None, orient=None, orient_k=12):
     """Register two clouds of any two sizes with neither a network nor a starting pose: src [B,3,Ns], tgt [B,3,Nt] (float32
     device tensors).  compute_fpfh_feature(k, radius) on both, match_features(mutual), ransac_correspondences(max_dist,
     trials, similarity, seed), then score_registration at max_dist on the FULL clouds (Open3D's closing evaluation).
@@ -206,9 +206,12 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     method: "ransac", or "fgr": fast_global_registration (``fgr``) takes the RANSAC's place -- no trial
     budget; trials, similarity and seed are not used, `fgr` is a dict of its keywords (tuple_scale, max_tuples, iterations,
     division_factor, mu_floor, decrease_mu, tuple_trials, seed).  The score and refine work from its pose in the same way.
+    "consistency": consistency_registration (``consistency``) takes the RANSAC's place -- pairwise
+    length-consistency voting, for matches of which most are wrong; trials, similarity and seed are not used, `consistency` is
+    a dict of its keywords (tau, keep, seeds, ratio, min_length).
     Returns a dict: fitness, inlier_rmse, inliers (the score of the global pose); R, t, best_trial, pairs and ransac_inliers
-    (the RANSAC's; its `inliers` under that name) -- with "fgr": R, t, pairs, tuples, used, status --; corr int32 [B,Ns]; and
-    with refine, `refined`: refine_registration's dict.
+    (the RANSAC's; its `inliers` under that name) -- with "fgr": R, t, pairs, tuples, used, status; with "consistency": R, t,
+    pairs, best_seed, consistency_inliers --; corr int32 [B,Ns]; and with refine, `refined`: refine_registration's dict.
     centre: False works in the caller's frame; True, or a pair (c_src, c_tgt) of [B,3] tensors, runs the whole chain --
     features, matching, RANSAC or FGR, score and refine -- on the clouds moved each to its own centre (``centred``), carries every
     pose back (``uncentred_pose``) and takes every score on the caller's clouds.  For clouds far from the origin relative to their
@@ -258,7 +261,8 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
         return _register_centred(src, tgt, max_dist, centre, refine,
                                  dict(k=k, radius=radius, mutual=mutual, trials=trials, similarity=similarity, seed=seed,
                                       refine=refine, refine_method=refine_method, src_normals=src_normals,
-                                      tgt_normals=tgt_normals, method=method, fgr=fgr, search=search, nn_search=nn_search,
+                                      tgt_normals=tgt_normals, method=method, fgr=fgr, consistency=consistency, search=search,
+                                      nn_search=nn_search,
                                       max_nn=max_nn, capacity=capacity, orient=orient, orient_k=orient_k,
                                       keypoints=keypoints, iss=iss or None, describe=describe))
     from .fpfh import compute_fpfh_feature
@@ -267,13 +271,18 @@ def register_features(src, tgt, max_dist, k=30, radius=None, mutual=True, trials
     api = "register_features"
     if refine is not None and not (math.isfinite(float(refine)) and float(refine) >= 0.0):
         raise VcrHipError(f"{api}: refine must be None or a finite correspondence cap >= 0, got {refine}")
-    if method not in ("ransac", "fgr"):
-        raise VcrHipError(f'{api}: method must be "ransac" or "fgr", got {method!r}')
+    if method not in ("ransac", "fgr", "consistency"):
+        raise VcrHipError(f'{api}: method must be "ransac" or "fgr" or "consistency", got {method!r}')
+    if fgr is not None and method != "fgr":
+        raise VcrHipError(f'{api}: fgr= holds the keywords of method="fgr"; the method is "{method}"')
+    if consistency is not None and method != "consistency":
+        raise VcrHipError(f'{api}: consistency= holds the keywords of method="consistency"; the method is "{method}"')
     if method == "fgr":
         return _register_fgr(api, src, tgt, max_dist, feat, mutual, refine, refine_method, src_normals, tgt_normals, fgr, nn_search,
                              orient, orient_k, keypoints, iss, describe)
-    if fgr is not None:
-        raise VcrHipError(f'{api}: fgr= holds the keywords of method="fgr"; the method is "ransac"')
+    if method == "consistency":
+        return _register_consistency(api, src, tgt, max_dist, feat, mutual, refine, refine_method, src_normals, tgt_normals,
+                                     consistency, nn_search, orient, orient_k, keypoints, iss, describe)
     _ransac_checks(api, src, tgt, None, max_dist, trials, similarity, seed, given_corr=False)
     keep, index = _keypoint_mask(src, keypoints, iss, describe)
 
@@ -404,6 +413,33 @@ def _register_fgr(api, src, tgt, max_dist, feat, mutual, refine, refine_method, 
         r = F.fast_global_registration(src, tgt, corr, **kw)
         res = dict(score_registration(src, tgt, r["R"], r["t"], max_dist, search=nn_search))
         res.update(R=r["R"], t=r["t"], pairs=r["pairs"], tuples=r["tuples"], used=r["used"], status=r["status"], corr=corr)
+        return res
+    res = _both_signs(src, tgt, src_normals, tgt_normals, feat, orient, orient_k, tail, index)
+    if refine is not None:
+        res["refined"] = refine_registration(src, tgt, res["R"], res["t"], float(refine), method=refine_method, search=nn_search)
+    return res
+
+
+def _register_consistency(api, src, tgt, max_dist, feat, mutual, refine, refine_method, src_normals, tgt_normals, kw,
+                          nn_search="scan", orient=None, orient_k=12, keypoints=None, iss=None, describe="all"):
+    """register_features with method="consistency": the same chain with consistency_registration in the RANSAC's place.  feat:
+    the keywords of both compute_fpfh_feature calls."""
+    from . import consistency as K
+    from .refine import refine_registration
+    from .score import score_registration
+    kw = {} if kw is None else kw
+    if not isinstance(kw, dict) or set(kw) - set(K.DEFAULTS):
+        raise VcrHipError(f"{api}: consistency must be None or a dict with keys among {sorted(K.DEFAULTS)}, got "
+                          f"{sorted(kw) if isinstance(kw, dict) else type(kw).__name__}")
+    kw = dict(K.DEFAULTS, **kw)
+    K._checks(api, src, tgt, None, max_dist, kw["tau"], kw["keep"], kw["seeds"], kw["ratio"], kw["min_length"], given_corr=False)
+    keep, index = _keypoint_mask(src, keypoints, iss, describe)
+
+    def tail(src_feat, tgt_feat):
+        corr = _placed(match_features(src_feat, tgt_feat, mutual=mutual), keep, index)
+        r = K.consistency_registration(src, tgt, corr, max_dist, **kw)
+        res = dict(score_registration(src, tgt, r["R"], r["t"], float(max_dist), search=nn_search))
+        res.update(R=r["R"], t=r["t"], pairs=r["pairs"], best_seed=r["best_seed"], consistency_inliers=r["inliers"], corr=corr)
         return res
     res = _both_signs(src, tgt, src_normals, tgt_normals, feat, orient, orient_k, tail, index)
     if refine is not None:
