@@ -19,7 +19,7 @@ __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "sco
            "model_resolution", "compute_point_cloud_distance", "compute_color_gradient", "refine_registration_colored",
            "refine_registration_robust", "information_matrix", "optimize_pose_graph", "pose_graph_from_clouds",
            "register_multiway", "compute_boundary_points", "smooth_mls", "consistency_registration",
-           "correspondence_consistency", "prune_correspondences"]
+           "correspondence_consistency", "prune_correspondences", "ndt_map", "ndt_derivatives", "refine_registration_ndt"]
 
 
 def __getattr__(name):
@@ -93,6 +93,9 @@ def __getattr__(name):
     if name in ("consistency_registration", "correspondence_consistency", "prune_correspondences"):
         from . import consistency
         return getattr(consistency, name)
+    if name in ("ndt_map", "ndt_derivatives", "refine_registration_ndt"):
+        from . import ndt
+        return getattr(ndt, name)
     if name in ("centred", "uncentred_pose"):
         from . import centre
         return getattr(centre, name)
