@@ -19,7 +19,8 @@ __all__ = ["weights", "synth", "farthest_point_sample", "register_sampled", "sco
            "model_resolution", "compute_point_cloud_distance", "compute_color_gradient", "refine_registration_colored",
            "refine_registration_robust", "information_matrix", "optimize_pose_graph", "pose_graph_from_clouds",
            "register_multiway", "compute_boundary_points", "smooth_mls", "consistency_registration",
-           "correspondence_consistency", "prune_correspondences", "ndt_map", "ndt_derivatives", "refine_registration_ndt"]
+           "correspondence_consistency", "prune_correspondences", "ndt_map", "ndt_derivatives", "refine_registration_ndt",
+           "coherent_point_drift", "cpd_expectation"]
 
 
 def __getattr__(name):
@@ -96,6 +97,9 @@ def __getattr__(name):
     if name in ("ndt_map", "ndt_derivatives", "refine_registration_ndt"):
         from . import ndt
         return getattr(ndt, name)
+    if name in ("coherent_point_drift", "cpd_expectation"):
+        from . import cpd
+        return getattr(cpd, name)
     if name in ("centred", "uncentred_pose"):
         from . import centre
         return getattr(centre, name)

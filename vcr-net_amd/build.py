@@ -45,10 +45,12 @@ MLS_HEADERS = [os.path.join(INCLUDE, "smooth", f) for f in ("vcr_hip_mls.h",)]
 CONSISTENCY_HEADERS = [os.path.join(INCLUDE, "consistency", f) for f in ("vcr_hip_consistency.h",)]
 # (... and consistency.o's: this one enters the digest of ndt.o ALONE)
 NDT_HEADERS = [os.path.join(INCLUDE, "ndt", f) for f in ("vcr_hip_ndt.h",)]
+# (... and ndt.o's: this one enters the digest of cpd.o ALONE)
+CPD_HEADERS = [os.path.join(INCLUDE, "cpd", f) for f in ("vcr_hip_cpd.h",)]
 OWN_HEADERS = {"support.hip": SUPPORT_HEADERS, "color_gradient.hip": COLORED_HEADERS, "refine_colored.hip": COLORED_HEADERS,
                "refine_robust.hip": ROBUST_HEADERS, "posegraph.hip": POSEGRAPH_HEADERS, "border.hip": BORDER_HEADERS,
                "mls.hip": MLS_HEADERS, "consistency.hip": CONSISTENCY_HEADERS,
-               "ndt.hip": NDT_HEADERS}
+               "ndt.hip": NDT_HEADERS, "cpd.hip": CPD_HEADERS}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off"]   # no silent a*b+c fusion: the kernels spell out every fmaf they want
